@@ -8,8 +8,15 @@
 A step is one forward pass of faster_vit_0_224 over one synthetic batch of 256 images per GPU (BASELINE configs[1]); inputs are
 resident in HBM before the timed region.  Inference is embarrassingly data parallel: every rank runs its own shard, there is no
 data-path collective; the only collectives are the barrier and the MAX / SUM reductions that turn per-rank
-timings into one whole-job figure.  Rank 0 prints ONE COMPACT JSON line (< 8 KB: the driver parses the last stdout line; r03's 26 KB
-line was cut by its stdout tail) and writes the full record to gpurun_out/bench_detail.json (untracked; --record PATH for a committed copy):
+timings into one whole-job figure.  Weights and inputs are seeded: the same arguments give the same inputs in every run.
+
+A plain run does what the headline figure needs and nothing else: set-up, W untimed + K timed steps, the outputs of the last timed
+step when --dump-outputs DIR is given (DIR/logits.npy, float32, one row per image; DIR/logits_rank<r>.npy per rank for N > 1), and
+ONE JSON line: metric, value, unit, n_gpus, steps, warmup, ms_per_step, higher_is_better, scaling, vs_baseline, dtype, data, config.
+
+--full adds everything below (as the default run did up to r06).  Rank 0 prints ONE COMPACT JSON line (< 8 KB: the driver parses the
+last stdout line; r03's 26 KB line was cut by its stdout tail) and writes the full record to bench_out/bench_detail.json (untracked;
+--record PATH for a committed copy):
 
   value / ms_per_step     W untimed + exactly K timed hipGraph replays, barrier + synchronize on both sides, MAX over ranks.  The graph
                           holds the deploy plan as 2 stream shards through level 2, joined, level 3 + head on the whole batch (--streams,
@@ -106,8 +113,13 @@ def parse():
     ap.add_argument("--secondary-steps", type=int, default=10)
     ap.add_argument("--secondary-streams", type=int, default=0, help="stream shards of the secondary configs' precise plan (0: the default, 2)")
     ap.add_argument("--no-modes", action="store_true", help="skip the parity / images-per-second legs of the other operand modes")
-    ap.add_argument("--record", default="", help="also write the full record to this path (e.g. profiles/r05_bench_final_detail.json); the default "
-                                                 "run writes only the untracked gpurun_out/bench_detail.json and leaves the work tree clean")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything else: step dispersion, roofline, parity against the CPU oracle, the other "
+                         "operand modes, the CPU baseline, the secondary configurations and the training step (the --no-* options prune it)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the logits of the last timed step to DIR/logits.npy (float32; DIR/logits_rank<r>.npy per rank for N > 1)")
+    ap.add_argument("--record", default="", help="--full: also write the full record to this path (e.g. profiles/r05_bench_final_detail.json); "
+                                                 "otherwise it goes only to the untracked bench_out/bench_detail.json and the work tree stays clean")
     ap.add_argument("--launch-selftest", action="store_true",
                     help="exercise ONLY the rank launch / barrier / reduction path on CPU (gloo), no model: prints n_gpus = ranks that ran")
     return ap.parse_args()
@@ -675,7 +687,8 @@ def run_train_step(args, dev, batch=64, steps=5, warmup=2):
 # the printed line: ONE compact JSON object (driver-parsed; < 8 KB, tests/test_bench_launch.py); everything else goes to a file
 # ------------------------------------------------------------------------------------------------------------------------
 LINE_BUDGET = 8000
-DETAIL_FILES = [os.path.join("gpurun_out", "bench_detail.json")]   # scratch (not tracked); --record PATH adds a copy meant to be committed
+DETAIL_FILES = [os.path.join("bench_out", "bench_detail.json")]   # scratch (not tracked); --record PATH adds a copy meant to be committed
+DUMP_BUDGET = 60 << 20   # --dump-outputs: bytes over all ranks (past it, a seeded sample of the images)
 _ROOF_KEYS = ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic", "traffic_over_algorithmic", "avg_launch_us", "median_launch_us",
               "outlier_launches_dropped", "avg_launch_us_rocprof", "frac_rocprof", "frac_serialized", "event_vs_rocprof", "timer_mismatch", "launches_per_step", "ms_per_step", "workgroups", "cu_share", "algorithmic_mflop_per_launch",
               "algorithmic_mbyte_per_launch", "timer")
@@ -686,13 +699,19 @@ def _pick(d, keys):
     return None if d is None else {k: d[k] for k in keys if k in d and d[k] is not None}
 
 
-def compact_line(out, detail_path=None):
-    """The driver-facing subset of the full record: the contract keys, the dominant-kernel roofline, the CPU baseline, parity of the timed
-    mode and of the two-term bf16 mode, three numbers per secondary configuration, and where the full record went."""
+def headline_line(out):
+    """The contract keys of the line and the timed configuration: all that a plain run prints."""
     c = {k: out.get(k) for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                                  "vs_baseline", "dtype", "data")}
     cfg = out.get("config") or {}
     c["config"] = {k: cfg[k] for k in ("workload", "global_batch", "parallelism", "hat_operands", "launch", "streams", "join_from") if k in cfg}
+    return c
+
+
+def compact_line(out, detail_path=None):
+    """The driver-facing subset of the full record: the contract keys, the dominant-kernel roofline, the CPU baseline, parity of the timed
+    mode and of the two-term bf16 mode, three numbers per secondary configuration, and where the full record went."""
+    c = headline_line(out)
     if "step_ms" in out:
         c["step_ms"] = _pick(out["step_ms"], ("n", "min", "median", "max"))
     c["roofline"] = _pick(out.get("roofline"), _ROOF_KEYS)
@@ -742,8 +761,23 @@ def compact_line(out, detail_path=None):
     return line
 
 
+def dump_outputs(out_dir, name, y, budget=DUMP_BUDGET):
+    """--dump-outputs: what the timed path returned in its last step (logits, one row per image) as out_dir/<name>.npy in float32.  Past `budget`
+    bytes a fixed seeded sample of rows is kept, and their indices go to out_dir/<name>_rows.npy (float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    a = y.detach().float().cpu().numpy()
+    row = max(a[:1].nbytes, 1)
+    if a.nbytes > budget:
+        rows = np.sort(np.random.default_rng(0).choice(a.shape[0], max(1, (budget - 8 * a.shape[0]) // row), replace=False))
+        np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+        a = a[rows]
+    np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    return os.path.join(out_dir, name + ".npy")
+
+
 def emit(out, record=""):
-    """Write the full record (gpurun_out/, plus --record PATH) and print the compact line as the LAST stdout line."""
+    """Write the full record (bench_out/, plus --record PATH) and print the compact line as the LAST stdout line."""
     path = None
     for rel in DETAIL_FILES + ([record] if record else []):
         try:
@@ -802,11 +836,19 @@ def main():
     cfg = Config(args, dev, rank, args.model, args.batch, hw=hw, model_kwargs=mk, streams=args.streams)
     cfg.prepare()
 
-    # W untimed + exactly K timed steps, barrier + synchronize on both sides, MAX over ranks
-    elapsed = dp.timed_steps(cfg.step, args.steps, args.warmup, torch.cuda.synchronize, dist, dev)
+    # W untimed + exactly K timed steps, barrier + synchronize on both sides, MAX over ranks; the output of the last step is kept (a reference)
+    last = [None]
+
+    def step():
+        last[0] = cfg.step()
+
+    elapsed = dp.timed_steps(step, args.steps, args.warmup, torch.cuda.synchronize, dist, dev)
+    if args.dump_outputs:   # before anything else runs: a runner's next step overwrites its output buffer
+        y = last[0] if last[0] is not None else cfg.free_runner.outputs()
+        dump_outputs(args.dump_outputs, "logits" if world == 1 else f"logits_rank{rank}", y, DUMP_BUDGET // world)
     value = dp.whole_job_rate(args.batch * args.steps, elapsed, dist, dev)
     n_ran = dp.ranks_that_ran(dist, dev)   # ranks that actually ran the timed region (== RCCL's group size)
-    logits_gpu = cfg.logits()
+    logits_gpu = cfg.logits() if args.full else None
     runners_diff = getattr(cfg, "runners_max_abs_diff", None)   # (of the timed operand mode: the later legs re-use the attribute)
 
     def finish():
@@ -818,7 +860,7 @@ def main():
     # host threads capped to its share of the cores; rank 0 reports the per-rank errors and their maximum.  After the timed region, so the
     # oracle's CPU work cannot disturb it.
     rank_parity = None
-    if dist is not None and not args.no_rank_parity and args.prof_steps > 0:
+    if args.full and dist is not None and not args.no_rank_parity and args.prof_steps > 0:
         arch_r = oracle_arch(args.model, mk)
         err_r = -1.0
         if arch_r is not None:
@@ -851,6 +893,9 @@ def main():
                    "launch": cfg.launch_desc(), "streams": cfg.streams,
                    "join_from": (getattr(cfg.plan, "join_from", None) if cfg.plan is not None else None)},
     }
+    if not args.full:   # a plain run: the headline figure and nothing else
+        print(json.dumps(headline_line(out), separators=(",", ":")), flush=True)
+        return finish()
     if args.prof_steps <= 0:   # timeline runs under rocprofv3 (scripts/gpu_trace.sh): nothing but the timed region
         out["roofline"] = None
         print(compact_line(out))

@@ -4,6 +4,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -155,3 +157,63 @@ def test_r06_final_record_carries_the_contract():
     tf = r["algorithmic_mflop_per_launch"] / float(rows[0]["AverageUs"])                         # MFLOP / us = TFLOP/s
     assert abs(tf / r["peak"] - r["frac"]) < 0.05 * r["frac"]
     assert c["cpu_baseline"]["kind"] == "port" and c["cpu_baseline"]["value"] > 0 and c["cpu_baseline"]["cores"] >= 1
+
+
+def test_plain_run_options_and_dumped_outputs(tmp_path):
+    """A plain `bench.py` run only times the headline (--full adds the rest); --dump-outputs writes float32 arrays within the byte budget and
+    samples a larger output with a fixed seed, so that two runs on the same arguments can be compared output for output."""
+    import numpy as np
+    import torch
+    import bench
+    old = sys.argv
+    try:
+        sys.argv = ["bench.py"]
+        a = bench.parse()
+        assert not a.full and a.dump_outputs == ""
+        sys.argv = ["bench.py", "--full", "--dump-outputs", str(tmp_path)]
+        a = bench.parse()
+        assert a.full and a.dump_outputs == str(tmp_path)
+    finally:
+        sys.argv = old
+    y = torch.randn(256, 1000, generator=torch.Generator().manual_seed(3)).half()
+    got = np.load(bench.dump_outputs(str(tmp_path / "a"), "logits", y))
+    assert got.dtype == np.float32 and np.array_equal(got, y.float().numpy()) and not os.path.exists(tmp_path / "a" / "logits_rows.npy")
+    big = torch.arange(4000 * 300, dtype=torch.float32).reshape(4000, 300)
+    b1 = np.load(bench.dump_outputs(str(tmp_path / "b"), "x", big, budget=1 << 20))
+    rows = np.load(tmp_path / "b" / "x_rows.npy")
+    b2 = np.load(bench.dump_outputs(str(tmp_path / "c"), "x", big, budget=1 << 20))
+    assert b1.nbytes + rows.nbytes <= 1 << 20 and rows.dtype == np.float64 and len(rows) == len(set(rows.tolist()))
+    assert np.array_equal(b1, b2) and np.array_equal(b1, big.numpy()[rows.astype(np.int64)])
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_dumps_the_timed_logits(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` on the headline configuration: one JSON line with the contract keys and exactly K
+    timed steps, and DIR/logits.npy = the logits of the last timed step, which agree with the CPU oracle on the same seeded weights and input."""
+    import numpy as np
+    import torch
+    import bench
+    import fastervit_amd
+    from oracle.model_reference import model_forward
+    from tests.synth import synth_state_dict
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=600, env=_env(), cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-4000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-4000:]
+    c = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "n_gpus"):
+        assert k in c, k
+    assert c["steps"] == 3 and c["warmup"] == 1 and c["n_gpus"] == 1 and c["dtype"] == "f16" and c["higher_is_better"] is True
+    assert abs(c["value"] - 256 * 1e3 / c["ms_per_step"]) < 0.01 * c["value"]
+    assert "roofline" not in c and "parity" not in c and "cpu_baseline" not in c          # the rest is --full's
+    got = np.load(tmp_path / "logits.npy")
+    assert got.dtype == np.float32 and got.shape == (256, 1000) and np.isfinite(got).all()
+    # the same weights and input as bench.Config (seeded), four images (both ends of the batch) through the fp32 CPU oracle
+    torch.manual_seed(0)
+    model = fastervit_amd.create_model("faster_vit_0_224").eval()
+    sd = synth_state_dict(model.state_dict(), seed=bench.WEIGHT_SEED, family="init")
+    x = torch.randn(256, 3, 224, 224, generator=torch.Generator(device="cpu").manual_seed(1000))
+    idx = [0, 1, 254, 255]
+    ref = model_forward(sd, x[idx], bench.oracle_arch("faster_vit_0_224", {})).numpy()
+    assert np.abs(got[idx] - ref).max() < 1e-3

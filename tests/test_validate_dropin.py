@@ -1,7 +1,8 @@
 """BASELINE configs[0]: the reference's own validate.py, unmodified, driving our model (plumbing, no GPU).
 
-Needs /root/reference (build container only).  The HAT stages have no CPU path in the product, so THIS TEST
-substitutes the CPU oracle for the stage executor -- test infrastructure standing in for the GPU, never shipped."""
+Runs the compiled copy of the reference's validate.py that build() leaves under oracle/_ref/ (oracle/build_ref.py; present where
+build() found an upstream checkout).  The HAT stages have no CPU path in the product, so THIS TEST substitutes the CPU oracle for
+the stage executor -- test infrastructure standing in for the GPU, never shipped."""
 import json
 import os
 import subprocess
@@ -10,8 +11,8 @@ import sys
 import pytest
 import torch
 
-REF = "/root/reference/fastervit/validate.py"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+REF = os.path.join(ROOT, "oracle", "_ref", "validate.pyc")
 
 DRIVER = r'''
 import sys, torch
@@ -33,7 +34,7 @@ run_reference_validate.main(sys.argv[1:])
 '''
 
 
-@pytest.mark.skipif(not os.path.isfile(REF), reason="reference checkout not present (GPU box)")
+@pytest.mark.skipif(not os.path.isfile(REF), reason="oracle/_ref/validate.pyc not built (build() found no upstream checkout)")
 def test_reference_validate_py_runs_unmodified(tmp_path):
     import fastervit_amd
     from tests.synth import synth_state_dict
