@@ -122,8 +122,11 @@ class PipelinedInference:
         # ``first``: an existing runner of the same configuration (slot base 0) to use as runner 0
         if first is not None and getattr(first.plan, "slot_base", 0) != 0:
             raise ValueError("PipelinedInference: the runner passed as `first` must use workspace slot base 0")
+        # runner i owns workspace slots [i * stride, (i + 1) * stride): the stride covers the stream shards of every runner, ``first`` included
+        # (a ``first`` with more shards than ``streams`` would otherwise share its upper slots -- and their split-kernel counters -- with runner 1)
+        stride = max(1, int(streams), first.plan.streams if first is not None else 1)
         self.runners = ([first] if first is not None else []) + \
-            [CompiledInference(model, example, streams=streams, slot_base=i * max(1, int(streams)), **kw) for i in range(1 if first is not None else 0, self.depth)]
+            [CompiledInference(model, example, streams=streams, slot_base=i * stride, **kw) for i in range(1 if first is not None else 0, self.depth)]
         self.device = example.device
         # cu_masks (experiment, r06): one CU bit mask (list of uint32 words, bit i = CU i of the runtime's numbering) per runner: its replays go to a stream created
         # with hipExtStreamCreateWithCUMask, i.e. the steps in flight are partitioned in SPACE (each on its own CUs) instead of sharing every CU in time

@@ -27,6 +27,15 @@ CASES = {
                                  hw=(576, 960), family="init", per_block=False,
                                  arch=_arch([3, 3, 12, 5], [4, 8, 16, 32], [7, 7, 12, 6], 196, [576, 960], prop=True,
                                             any_res=True)),
+    # ---- FasterViT-0 any-res geometries of the fused C = 256 / 512 kernels ("stress" weights, image-0 stage maps) ----
+    # stage 2 is 7x14 (sr (1, 2), G = 8: a non-square carrier grid, no hat_pos_embed), stage 3 is 4x7 -> padded 7x7
+    "fvit0_anyres_112x224": dict(entry="faster_vit_0_any_res", kwargs=dict(resolution=[112, 224]), batch=2, hw=(112, 224), family="stress",
+                                 per_block=False, stage_maps=True,
+                                 arch=_arch([2, 3, 6, 5], [2, 4, 8, 16], [7, 7, 7, 7], 64, [112, 224], any_res=True)),
+    # stage 2 is 10x10 -> padded 14x14 (pad tokens take part in attention, then get cropped), stage 3 5x5 -> 7x7; layer scale + propagation
+    "fvit0_anyres_160x160": dict(entry="faster_vit_0_any_res", kwargs=dict(resolution=[160, 160], layer_scale=1e-5, do_propagation=True),
+                                 batch=2, hw=(160, 160), family="stress", per_block=False, stage_maps=True,
+                                 arch=_arch([2, 3, 6, 5], [2, 4, 8, 16], [7, 7, 7, 7], 64, [160, 160], prop=True, any_res=True)),
     # ---- ImageNet-21k fine-tune geometries with ONE long window per image in stage 2 (576 / 2304 tokens): logits only ----
     "fvit4_21k_384": dict(entry="faster_vit_4_21k_384", kwargs={}, batch=1, hw=(384, 384), family="init", per_block=False,
                           arch=_arch([3, 3, 12, 5], [4, 8, 16, 32], [7, 7, 24, 12], 196, 384, hat=[False] * 4, prop=True)),

@@ -9,7 +9,8 @@ within fp32 summation-order noise, and themselves repeatable.
 import pytest
 import torch
 
-from fastervit_amd import _lib, hat_runtime
+from fastervit_amd import hat_runtime
+from tests.util import tuned
 
 pytestmark = pytest.mark.gpu
 
@@ -125,33 +126,25 @@ print("POISON-OK")
     assert res.returncode == 0 and "POISON-OK" in res.stdout, res.stdout[-3000:]
 
 
-_DEFAULTS = {"gemm_stagger": 0, "ab_stagger": 0, "mlp_stagger": 0, "ab_variant": 0,
-             "attn_fused_min_rows": 16384, "mlp_fused_min_rows": 16384, "ln_gemm": 0, "ct_fused": 1, "ct_variant": 3, "ct_touch": 0, "win_fused": 1, "win_mlp": 1, "win_fused256": 0,
-             "win_mlp_pipe": 1, "ct8_depth": 3}
+# every knob set the sweep below runs (tests/test_tune_knobs.py checks each key against the tune_get calls of the HIP sources)
+KNOB_SETS = [dict(gemm_stagger=1), dict(ab_stagger=1, mlp_stagger=1), dict(mlp_stagger=2), dict(ab_variant=2),
+             dict(ab_variant=1),
+             dict(attn_fused_min_rows=0, mlp_fused_min_rows=0), dict(ln_gemm=1), dict(ct_fused=0), dict(ct_variant=0), dict(ct_variant=1), dict(ct_variant=2), dict(ct_variant=0, ct_touch=1), dict(win_fused=0), dict(win_mlp=0), dict(win_mlp=0, win_fused=0, ln_gemm=1), dict(win_fused256=1), dict(win_mlp_pipe=0), dict(ct8_depth=2)]
 
 
-@pytest.mark.parametrize("knobs", [dict(gemm_stagger=1), dict(ab_stagger=1, mlp_stagger=1), dict(mlp_stagger=2), dict(ab_variant=2),
-                                   dict(ab_variant=1),
-                                   dict(attn_fused_min_rows=0, mlp_fused_min_rows=0), dict(ln_gemm=1), dict(ct_fused=0), dict(ct_variant=0), dict(ct_variant=1), dict(ct_variant=2), dict(ct_variant=0, ct_touch=1), dict(win_fused=0), dict(win_mlp=0), dict(win_mlp=0, win_fused=0, ln_gemm=1), dict(win_fused256=1), dict(win_mlp_pipe=0), dict(ct8_depth=2)])
+@pytest.mark.parametrize("knobs", KNOB_SETS)
 def test_order_stagger_knobs_keep_the_result(knobs):
     """Kernel-selection knobs (K / chunk / head order stagger, LDS ring depths, workgroup shapes, fused vs unfused carrier branch) only
     permute fp32 sums or change who computes what: same stage output within summation-order noise, still bit-repeatable."""
     model = _model("faster_vit_0_224")
     g = torch.Generator(device="cpu").manual_seed(5)
-    try:
-        for li, R, C in ((2, 14, 256), (3, 7, 512)):
-            lvl = model.levels[li]
-            x = torch.randn(96, C, R, R, generator=g).cuda()
-            ref = hat_runtime.stage_forward(lvl, x).clone()
-            for k, v in knobs.items():
-                _lib.tune(k, v)
+    for li, R, C in ((2, 14, 256), (3, 7, 512)):
+        lvl = model.levels[li]
+        x = torch.randn(96, C, R, R, generator=g).cuda()
+        ref = hat_runtime.stage_forward(lvl, x).clone()
+        with tuned(**knobs):
             a = hat_runtime.stage_forward(lvl, x).clone()
             b = hat_runtime.stage_forward(lvl, x).clone()
-            for k in knobs:
-                _lib.tune(k, _DEFAULTS[k])
-            assert torch.equal(a, b)
-            err = (a - ref).abs().max().item()
-            assert err < 2e-4 * max(ref.abs().max().item(), 1.0), f"level {li}: {err}"   # fp16 operands re-rounded after a different fp32 sum order
-    finally:
-        for k in knobs:
-            _lib.tune(k, _DEFAULTS[k])
+        assert torch.equal(a, b)
+        err = (a - ref).abs().max().item()
+        assert err < 2e-4 * max(ref.abs().max().item(), 1.0), f"level {li}: {err}"   # fp16 operands re-rounded after a different fp32 sum order

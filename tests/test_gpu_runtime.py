@@ -97,6 +97,37 @@ def test_pipelined_steps_in_flight_vs_oracle(depth, streams, join_from):
     assert torch.equal(o2[0], outs[0]) and max_abs(o2[1], outs[0].flip(0)) < 2e-4   # (an image's rows sit in other tiles: same values to rounding order)
 
 
+def test_pipelined_first_runner_with_more_shards_keeps_its_own_slots():
+    """``PipelinedInference(first=...)`` with a ``first`` compiled for MORE stream shards (3) than the pipeline's own runners (1): the runners' stage-
+    workspace slot ranges must not overlap (before the fix runner 1 started at slot 1, inside runner 0's slots 0..2, so two graphs in flight could share
+    stage workspaces and the split-kernel counters in them).  After a burst of overlapped launches every runner's logits equal those of a single
+    runner of its own configuration bit for bit, and match the fp32 CPU oracle on a subset of images."""
+    model, sd = build_product_model("fvit0_224", "cuda")
+    model = model.to(memory_format=torch.channels_last)
+    x_cpu = torch.randn(48, 3, 224, 224, generator=torch.Generator(device="cpu").manual_seed(77))
+    x = x_cpu.cuda().contiguous(memory_format=torch.channels_last)
+    first = CompiledInference(model, x, dtype=torch.float16, streams=3)
+    pipe = PipelinedInference(model, x, depth=3, streams=1, first=first, dtype=torch.float16)
+    assert pipe.runners[0] is first
+    ranges = [set(range(r.plan.slot_base, r.plan.slot_base + r.plan.streams)) for r in pipe.runners]
+    for i in range(len(ranges)):
+        for j in range(i + 1, len(ranges)):
+            assert not (ranges[i] & ranges[j]), f"runners {i} and {j} share workspace slots {sorted(ranges[i] & ranges[j])}"
+    for _ in range(7):                      # a burst: steps overlap on the GPU
+        pipe.launch()
+    outs = [o.float().cpu().clone() for o in pipe.outputs()]
+    single3 = CompiledInference(model, x, dtype=torch.float16, streams=3, slot_base=16)(x).float().cpu()
+    single1 = CompiledInference(model, x, dtype=torch.float16, streams=1, slot_base=16)(x).float().cpu()
+    assert torch.equal(outs[0], single3)
+    for o in outs[1:]:
+        assert torch.equal(o, single1)
+    idx = [1, 17, 40]                       # one image from each of runner 0's shards
+    ref = model_forward(sd, x_cpu[idx], CASES["fvit0_224"]["arch"])
+    errs = [max_abs(o[idx], ref) for o in outs]
+    print(f"pipelined first(streams=3) + streams=1 runners: logits max-abs err {errs} (|logits| max {ref.abs().max():.3f})")
+    assert max(errs) < 1e-3
+
+
 def test_compiled_inference_rejects_wrong_inputs():
     model, _ = build_product_model("tiny_hier", "cuda")
     x = case_input("tiny_hier").cuda()

@@ -14,7 +14,7 @@ from tests.cases import CASES
 from tests.util import GOLDEN_DIR, build_product_model, case_input, load_golden, max_abs
 
 TINY = [n for n, c in CASES.items() if c["per_block"]]
-FULL_FAST = ["fvit0_224", "fvit0_224_stress"]
+FULL_FAST = ["fvit0_224", "fvit0_224_stress", "fvit0_anyres_112x224", "fvit0_anyres_160x160"]
 FULL_SLOW = ["fvit4_224", "fvit4_anyres_576x960", "fvit4_21k_384"]
 
 
