@@ -1,0 +1,180 @@
+// fvit_backbone.hip -- the two memory-bound passes of the multi-scale detection backbone (fastervit_amd/models/backbone.py):
+//   * fvit_token_init_dyn : TokenInitializer of the detection variant (DINO fastervit.py:542-592): depthwise 3x3 + bias, average pool with
+//                           kernel / stride derived from the padded map on each call, zero pad to a multiple of ct_size, and the raw
+//                           NCHW -> (Hq*Wq, C) reshape (no permute) of that module.  One workgroup per (image, channel) plane: the conv
+//                           output plane is staged in LDS, the overlapping pool windows read it from there, the pooled plane is written
+//                           contiguously (that IS the (B, G, C) row order of the reference reshape).
+//   * fvit_feature_tap    : crop + folded eval BatchNorm2d + contiguous NCHW fp32 of one pre-downsample stage map (fastervit.py:835-838),
+//                           from any strided view (NCHW, channels_last, a crop of a padded map).  32-channel x 64-pixel tiles through LDS, so
+//                           that both the read (along whichever of C / W is unit-stride) and the NCHW write are coalesced.
+#include "fvit_common.h"
+
+namespace fvit {
+
+namespace {
+
+constexpr int kTokLdsFloats = 16384;   // 64 KiB: conv-output planes up to 16384 pixels (a 128 x 128 stage-2 map, ~2048 x 2048 images)
+
+template <typename IN>
+__device__ __forceinline__ float ld_map(const IN* p, int64_t off) { return (float)p[off]; }
+
+struct TokDynParams {
+    FvitMapView in;
+    const float* w;      // [C][9]
+    const float* bias;   // [C]
+    float* out;          // (B, C, Hq, Wq) contiguous == the reference's (B, Hq*Wq, C) reshape
+    int B, C, Hp, Wp, kh, kw, sh, sw, Ho, Wo, Hq, Wq;
+    float inv_area;
+};
+
+template <typename IN>
+__global__ __launch_bounds__(256) void token_init_dyn_kernel(TokDynParams p) {
+    __shared__ float conv[kTokLdsFloats];
+    const int plane = blockIdx.x;            // b * C + c
+    const int c = plane % p.C, b = plane / p.C;
+    const IN* __restrict__ src = (const IN*)p.in.data + (int64_t)b * p.in.stride_b + (int64_t)c * p.in.stride_c;
+    float wv[9];
+#pragma unroll
+    for (int j = 0; j < 9; ++j) wv[j] = p.w[c * 9 + j];
+    const float bv = p.bias[c];
+    const int npix = p.Hp * p.Wp;
+    // depthwise 3x3, zero padding 1 (threads walk the plane along W: unit-stride reads for NCHW maps)
+    for (int i = threadIdx.x; i < npix; i += blockDim.x) {
+        const int y = i / p.Wp, x = i - y * p.Wp;
+        float acc = bv;
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky) {
+            const int yy = y + ky - 1;
+            if (yy < 0 || yy >= p.Hp) continue;
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx) {
+                const int xx = x + kx - 1;
+                if (xx < 0 || xx >= p.Wp) continue;
+                acc += wv[ky * 3 + kx] * ld_map(src, (int64_t)yy * p.in.stride_h + (int64_t)xx * p.in.stride_w);
+            }
+        }
+        conv[i] = acc;
+    }
+    __syncthreads();
+    // average pool (padding 0, floor mode: divisor kh * kw) + zero pad to Hq x Wq
+    float* __restrict__ dst = p.out + (int64_t)plane * p.Hq * p.Wq;
+    const int nq = p.Hq * p.Wq;
+    for (int i = threadIdx.x; i < nq; i += blockDim.x) {
+        const int oy = i / p.Wq, ox = i - oy * p.Wq;
+        float s = 0.f;
+        if (oy < p.Ho && ox < p.Wo) {
+            const int y0 = oy * p.sh, x0 = ox * p.sw;
+            for (int dy = 0; dy < p.kh; ++dy) {
+                const float* row = conv + (y0 + dy) * p.Wp + x0;
+                for (int dx = 0; dx < p.kw; ++dx) s += row[dx];
+            }
+            s *= p.inv_area;
+        }
+        dst[i] = s;
+    }
+}
+
+struct TapParams {
+    FvitMapView in;
+    const float* scale;   // [C]
+    const float* shift;   // [C]
+    float* out;           // (B, C, H, W) contiguous
+    int B, C, H, W, ctiles, wtiles;
+    int c_fast;           // the view is unit-stride along C (channels_last): read with lanes along C
+};
+
+template <typename IN>
+__global__ __launch_bounds__(256) void feature_tap_kernel(TapParams p) {
+    __shared__ float tile[32][65];
+    int t = blockIdx.x;
+    const int wt = t % p.wtiles; t /= p.wtiles;
+    const int ct = t % p.ctiles; t /= p.ctiles;
+    const int h = t % p.H, b = t / p.H;
+    const int c0 = ct * 32, w0 = wt * 64;
+    const IN* __restrict__ src = (const IN*)p.in.data + (int64_t)b * p.in.stride_b + (int64_t)h * p.in.stride_h;
+    if (p.c_fast) {
+        const int cl = threadIdx.x & 31;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int wl = (threadIdx.x >> 5) + 8 * k;
+            const int cc = c0 + cl, ww = w0 + wl;
+            tile[cl][wl] = (cc < p.C && ww < p.W) ? ld_map(src, (int64_t)cc * p.in.stride_c + (int64_t)ww * p.in.stride_w) : 0.f;
+        }
+    } else {
+        const int wl = threadIdx.x & 63;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int cl = (threadIdx.x >> 6) + 4 * k;
+            const int cc = c0 + cl, ww = w0 + wl;
+            tile[cl][wl] = (cc < p.C && ww < p.W) ? ld_map(src, (int64_t)cc * p.in.stride_c + (int64_t)ww * p.in.stride_w) : 0.f;
+        }
+    }
+    __syncthreads();
+    const int wl = threadIdx.x & 63, ww = w0 + wl;
+    if (ww >= p.W) return;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const int cl = (threadIdx.x >> 6) + 4 * k, cc = c0 + cl;
+        if (cc < p.C)
+            p.out[(((int64_t)b * p.C + cc) * p.H + h) * p.W + ww] = tile[cl][wl] * p.scale[cc] + p.shift[cc];
+    }
+}
+
+}  // namespace
+
+}  // namespace fvit
+
+using namespace fvit;
+
+extern "C" int fvit_token_init_dyn(const FvitMapView* in, const float* weight, const float* bias, float* ct_out, int32_t batch, int32_t C,
+                                   int32_t Hp, int32_t Wp, int32_t pool_kh, int32_t pool_kw, int32_t pool_sh, int32_t pool_sw, int32_t cw,
+                                   fvit_stream_t stream) {
+    if (!in || !in->data || !weight || !bias || !ct_out) { set_error("token_init_dyn: null argument"); return FVIT_EINVAL; }
+    TokDynParams p;
+    p.in = *in; p.w = weight; p.bias = bias; p.out = ct_out; p.B = batch; p.C = C; p.Hp = Hp; p.Wp = Wp;
+    p.kh = pool_kh; p.kw = pool_kw; p.sh = pool_sh; p.sw = pool_sw;
+    if (batch <= 0 || C <= 0 || Hp <= 0 || Wp <= 0 || pool_kh <= 0 || pool_kw <= 0 || pool_sh <= 0 || pool_sw <= 0 || cw <= 0 ||
+        pool_kh > Hp || pool_kw > Wp) {
+        set_error("token_init_dyn: bad geometry B=%d C=%d map %dx%d pool k=%dx%d s=%dx%d cw=%d", batch, C, Hp, Wp, pool_kh, pool_kw, pool_sh,
+                  pool_sw, cw);
+        return FVIT_EINVAL;
+    }
+    if ((int64_t)Hp * Wp > kTokLdsFloats) {
+        set_error("token_init_dyn: %dx%d map exceeds the %d-pixel LDS plane", Hp, Wp, kTokLdsFloats);
+        return FVIT_EINVAL;
+    }
+    p.Ho = (Hp - pool_kh) / pool_sh + 1;
+    p.Wo = (Wp - pool_kw) / pool_sw + 1;
+    p.Hq = (p.Ho + cw - 1) / cw * cw;
+    p.Wq = (p.Wo + cw - 1) / cw * cw;
+    p.inv_area = 1.0f / (float)(pool_kh * pool_kw);
+    const int64_t planes = (int64_t)batch * C;
+    ProfScope prof(FVIT_K_OTHER, 2.0 * planes * ((double)Hp * Wp * 9 + (double)p.Ho * p.Wo * pool_kh * pool_kw),
+                   (double)planes * Hp * Wp * (in->dtype == FVIT_F32 ? 4.0 : 2.0) + 4.0 * planes * p.Hq * p.Wq, (hipStream_t)stream);
+    const dim3 grid((unsigned)planes);
+    if (in->dtype == FVIT_F32) hipLaunchKernelGGL((token_init_dyn_kernel<float>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    else if (in->dtype == FVIT_F16) hipLaunchKernelGGL((token_init_dyn_kernel<_Float16>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    else if (in->dtype == FVIT_BF16) hipLaunchKernelGGL((token_init_dyn_kernel<__bf16>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    else { set_error("token_init_dyn: map dtype %d not supported", in->dtype); return FVIT_EINVAL; }
+    return check_launch("token_init_dyn_kernel");
+}
+
+extern "C" int fvit_feature_tap(const FvitMapView* in, int32_t batch, int32_t C, int32_t H, int32_t W, const float* scale, const float* shift,
+                                float* out, fvit_stream_t stream) {
+    if (!in || !in->data || !scale || !shift || !out) { set_error("feature_tap: null argument"); return FVIT_EINVAL; }
+    if (batch <= 0 || C <= 0 || H <= 0 || W <= 0) { set_error("feature_tap: bad shape B=%d C=%d %dx%d", batch, C, H, W); return FVIT_EINVAL; }
+    TapParams p;
+    p.in = *in; p.scale = scale; p.shift = shift; p.out = out; p.B = batch; p.C = C; p.H = H; p.W = W;
+    p.ctiles = (C + 31) / 32; p.wtiles = (W + 63) / 64;
+    p.c_fast = (in->stride_c == 1 && in->stride_w != 1) ? 1 : 0;
+    const int64_t blocks = (int64_t)batch * H * p.ctiles * p.wtiles;
+    if (blocks > 0x7fffffff) { set_error("feature_tap: grid too large"); return FVIT_EINVAL; }
+    const double n = (double)batch * C * H * W;
+    ProfScope prof(FVIT_K_OTHER, 2.0 * n, n * ((in->dtype == FVIT_F32 ? 4.0 : 2.0) + 4.0), (hipStream_t)stream);
+    const dim3 grid((unsigned)blocks);
+    if (in->dtype == FVIT_F32) hipLaunchKernelGGL((feature_tap_kernel<float>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    else if (in->dtype == FVIT_F16) hipLaunchKernelGGL((feature_tap_kernel<_Float16>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    else if (in->dtype == FVIT_BF16) hipLaunchKernelGGL((feature_tap_kernel<__bf16>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    else { set_error("feature_tap: map dtype %d not supported", in->dtype); return FVIT_EINVAL; }
+    return check_launch("feature_tap_kernel");
+}

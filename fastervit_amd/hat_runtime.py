@@ -17,6 +17,7 @@ Constant folding (done once per weight version):
 """
 from __future__ import annotations
 
+import collections
 import contextlib
 import ctypes as C
 import threading
@@ -262,17 +263,38 @@ def frag_pack_fc2(w2: torch.Tensor) -> torch.Tensor:
     return t.permute(2, 0, 3, 1, 4).contiguous()                                           # j, cb, g, s, e
 
 
-def pack_block(blk, S: int, G: int, dpad: int, op_dtype, keep: _Keep) -> FvitBlockWeights:
+@torch.no_grad()
+def grid_pos_table(pe, h: int, w: int) -> torch.Tensor:
+    """(h*w, dim) fp32: PosEmbMLPSwinv1D.forward(x, h_g, w_g) of the detection backbone (DINO fastervit.py:176-203): the grid is
+    arange(h) x arange(w) in raster order, shifted and divided by (h*w) // 2 -- the TOKEN count, where the classifier's ``table()`` uses
+    sqrt(tokens) // 2.  Used for the window table (h = w = ws) and the rectangular carrier table (h, w = carrier grid)."""
+    n = h * w
+    w0 = pe.cpb_mlp[0].weight
+    ys = torch.arange(h, device=w0.device, dtype=torch.float32)
+    xs = torch.arange(w, device=w0.device, dtype=torch.float32)
+    grid = torch.stack(torch.meshgrid(ys, xs, indexing="ij")).reshape(2, n).t()
+    grid = (grid - (n // 2)) / (n // 2)
+    with torch.autocast(device_type=w0.device.type, enabled=False):
+        hid = torch.relu(F.linear(grid, w0.float(), pe.cpb_mlp[0].bias.float()))
+        return F.linear(hid, pe.cpb_mlp[2].weight.float()).float().contiguous()
+
+
+def pack_block(blk, S: int, G: int, dpad: int, op_dtype, keep: _Keep, grid=None) -> FvitBlockWeights:
+    """``grid`` = (hg, wg) carrier grid of a dynamic-grid (detection backbone) layer: its position tables follow the detection variant's
+    formulas (grid_pos_table); None: the classifier's."""
     w = FvitBlockWeights()
     w.attn = pack_attention(blk.attn, blk.norm1, blk.gamma3, S, dpad, op_dtype, keep)
     w.mlp = pack_mlp(blk.mlp, blk.norm2, blk.gamma4, op_dtype, keep)
-    w.pe_x = keep.ptr(blk.pos_embed.table(blk.window_size ** 2))
+    ws = blk.window_size
+    w.pe_x = keep.ptr(blk.pos_embed.table(ws ** 2) if grid is None else grid_pos_table(blk.pos_embed, ws, ws))
     w.pe_ct = None
     if blk.do_sr_hat:
+        # (dynamic grids: G carrier tokens against a bias table built for the build-time grid -- PosEmbMLPSwinv2D.table pads it top / left
+        #  for G > its size and crops it for G < its size, as F.pad does in the reference)
         w.hat_attn = pack_attention(blk.hat_attn, blk.hat_norm1, blk.gamma1, G, dpad, op_dtype, keep)
         w.hat_mlp = pack_mlp(blk.hat_mlp, blk.hat_norm2, blk.gamma2, op_dtype, keep)
         if hasattr(blk, "hat_pos_embed"):
-            w.pe_ct = keep.ptr(blk.hat_pos_embed.table(G))
+            w.pe_ct = keep.ptr(blk.hat_pos_embed.table(G) if grid is None else grid_pos_table(blk.hat_pos_embed, *grid))
     w.last = 1 if blk.last else 0
     return w
 
@@ -316,6 +338,7 @@ class StageState:
         self.blocks_c = None
         self.tables = {}      # (Hp, Wp) -> (dict of device tensors, FvitStageTables)
         self.workspaces = {}  # (B, Hp, Wp, H, W, operand dtype, slot) -> _Workspace
+        self.packs = collections.OrderedDict()   # dynamic-grid layers: (Hp, Wp) -> (sig, _Keep, FvitBlockWeights array), LRU
         self.lock = threading.RLock()   # packing and the launches of one stage are enqueued under this lock
 
 
@@ -338,12 +361,34 @@ def _state(layer, device) -> StageState:
         return st
 
 
+#: geometries (padded stage-input sizes) whose tables, packed weights and workspaces a dynamic-grid layer keeps (LRU)
+DYN_CACHE_SIZE = 8
+_PACKS = 0   # weight packings done by this process (tests count them)
+
+
+def pack_count() -> int:
+    """Number of times a layer's weights were packed in this process (repacking is the expensive part of a geometry change)."""
+    return _PACKS
+
+
+def _lru_touch(d: dict, key, limit: int, on_evict=None) -> None:
+    """Move ``key`` to the young end of ``d`` (insertion order) and drop the oldest entries beyond ``limit``."""
+    d[key] = d.pop(key)
+    while len(d) > limit:
+        old = next(iter(d))
+        v = d.pop(old)
+        if on_evict is not None:
+            on_evict(v)
+
+
 def _geometry(layer, Hp: int, Wp: int):
+    """Dynamic-grid layers (the detection backbone, ``layer.dynamic_grid``) take the window grid of every call from the padded input; every
+    other layer must see the grid it was built for."""
     blk = layer.blocks[0]
     ws = layer.window_size
     hier = bool(blk.do_sr_hat)
     sr0, sr1 = Hp // ws, Wp // ws
-    if hier and [sr0, sr1] != list(blk.sr_ratio):
+    if hier and not getattr(layer, "dynamic_grid", False) and [sr0, sr1] != list(blk.sr_ratio):
         raise ValueError(f"hierarchical stage was built for {blk.sr_ratio[0]}x{blk.sr_ratio[1]} windows of {ws}; "
                          f"the (padded) input has {sr0}x{sr1}")
     return ws, hier, sr0, sr1
@@ -383,6 +428,8 @@ def _prepare(layer, x_dev, Hp: int, Wp: int):
     if d > 96:
         raise NotImplementedError(f"head_dim {d} > 96 has no attention kernel instance")
     dpad = 32 if d <= 32 else (64 if d <= 64 else 96)   # 96: head_dim 80 of FasterViT-5 / -6
+    global _PACKS
+    dyn = bool(getattr(layer, "dynamic_grid", False)) and hier   # (a local-only stage packs the same weights at every size)
     tkey = (Hp, Wp)
     if tkey not in st.tables:
         tb = build_tables(sr0, sr1, ws, cw, hier)
@@ -390,16 +437,27 @@ def _prepare(layer, x_dev, Hp: int, Wp: int):
         ct = FvitStageTables(dev_t["ln1_src"].data_ptr(), dev_t["ln1_add"].data_ptr(), dev_t["ct_src"].data_ptr(),
                              dev_t["up_idx"].data_ptr())
         st.tables[tkey] = (tb, dev_t, ct)
+    if getattr(layer, "dynamic_grid", False):
+        _lru_touch(st.tables, tkey, DYN_CACHE_SIZE)
     tb, _, ctables = st.tables[tkey]
     sig = _signature(layer.blocks, x_dev, op_name, bool(getattr(layer, "_is_replica", False))) + (tb["S"], tb["G"])
-    if st.sig != sig:
+    hit = st.packs.get(tkey) if dyn else None
+    if dyn and hit is not None and hit[0] == sig:
+        _lru_touch(st.packs, tkey, DYN_CACHE_SIZE)
+        st.sig, st.keep, st.blocks_c = hit
+    elif st.sig != sig or dyn:
         keep = _Keep(op_dtype, terms)
         arr = (FvitBlockWeights * len(layer.blocks))()
+        grid = (cw * sr0, cw * sr1) if getattr(layer, "dynamic_grid", False) else None   # detection-variant position tables
         # constant folding must not run under the caller's autocast: the tables are fp32 by contract
         with torch.autocast(device_type="cuda", enabled=False):
             for i, blk in enumerate(layer.blocks):
-                arr[i] = pack_block(blk, tb["S"], tb["G"], dpad, op_dtype, keep)
+                arr[i] = pack_block(blk, tb["S"], tb["G"], dpad, op_dtype, keep, grid=grid)
         st.keep, st.blocks_c, st.sig = keep, arr, sig
+        _PACKS += 1
+        if dyn:
+            st.packs[tkey] = (sig, keep, arr)
+            _lru_touch(st.packs, tkey, DYN_CACHE_SIZE)
     lib = _lib.lib()
     desc_common = dict(C=Cdim, heads=heads, dpad=dpad, ws=ws, Hp=Hp, Wp=Wp, cw=cw if hier else 0, hier=int(hier),
                        square=int(hier and hasattr(blk0, "hat_pos_embed")), hidden=blk0.mlp.fc1.out_features,
@@ -433,13 +491,20 @@ def workspace_slot(slot: int):
         set_workspace_slot(prev)
 
 
-def _workspace(st: StageState, desc_common: dict, B: int, H: int, W: int, device) -> _Workspace:
+def _drop_workspace(w: _Workspace) -> None:
+    if w.event is not None:
+        w.event.synchronize()   # the evicted scratch may still be in use by a stage enqueued on another stream
+
+
+def _workspace(st: StageState, desc_common: dict, B: int, H: int, W: int, device, bounded: bool = False) -> _Workspace:
     # (the workspace LAYOUT is the same for one- and two-term weights -- activations are single-rounded there -- but the descriptor
     # carries the terms: one scratch buffer per key, one descriptor per weight-term count; the x3 modes hold two-term activation
     # rows and get their own buffer)
     terms = desc_common["weight_terms"]
     key = (B, desc_common["Hp"], desc_common["Wp"], H, W, desc_common["operand_dtype"], _slot()) + (("x3",) if terms == 3 else ())
     hit = st.workspaces.get(key)
+    if hit is not None and bounded:
+        _lru_touch(st.workspaces, key, DYN_CACHE_SIZE, _drop_workspace)
     if hit is not None:
         d = hit.descs.get(terms)
         if d is None:
@@ -454,6 +519,8 @@ def _workspace(st: StageState, desc_common: dict, B: int, H: int, W: int, device
     ws_t = torch.zeros(nbytes, dtype=torch.uint8, device=device)  # zero-filled once, dedicated to this geometry
     ws = st.workspaces[key] = _Workspace(desc, ws_t)
     ws.descs[terms] = desc
+    if bounded:   # dynamic-grid layers see a new (B, H, W) on every detection batch: keep the most recent few
+        _lru_touch(st.workspaces, key, DYN_CACHE_SIZE, _drop_workspace)
     return ws
 
 
@@ -484,22 +551,7 @@ def token_init(tok, xp: torch.Tensor) -> torch.Tensor:
     in one HIP kernel, f32 (B, G, C) out.  (MIOpen runs this depthwise conv on its naive path: ~150 us at B = 256.)"""
     _require_gpu(xp, "TokenInitializer")
     with torch.no_grad(), torch.cuda.device(xp.device):
-        key = "_fvit_tok"
-        cache = tok.__dict__.get(key)
-        if not isinstance(cache, dict):
-            cache = tok.__dict__[key] = {}
-        wt, bs = tok.pos_embed.weight, tok.pos_embed.bias
-        if wt.device != xp.device:
-            raise RuntimeError(f"TokenInitializer: parameters are on {wt.device} but the input is on {xp.device}")
-        replica = bool(getattr(tok, "_is_replica", False))
-        sig = (float(wt.detach().float().sum()), float(bs.detach().float().sum())) if replica else \
-            (wt.data_ptr(), wt._version, bs.data_ptr(), bs._version)
-        st = cache.get(str(xp.device))
-        if st is None or st[0] != sig:
-            w = wt.detach().float().reshape(-1, 9).contiguous()
-            b = bs.detach().float().contiguous()
-            st = cache[str(xp.device)] = (sig, w, b)
-        _, w, b = st
+        w, b = _token_weights(tok, xp)
         pool = tok.to_global_feature.pool
         kh, kw = pool.kernel_size if isinstance(pool.kernel_size, (tuple, list)) else (pool.kernel_size,) * 2
         sh, sw = pool.stride if isinstance(pool.stride, (tuple, list)) else (pool.stride,) * 2
@@ -511,6 +563,104 @@ def token_init(tok, xp: torch.Tensor) -> torch.Tensor:
                                         tok.window_size, _stream_ptr(xp.device))
         _lib.check(rc, "fvit_token_init")
         return ct
+
+
+def _token_weights(tok, xp: torch.Tensor):
+    """f32 depthwise weight (C, 9) and bias (C,) of a TokenInitializer on the input's device, cached per weight version."""
+    key = "_fvit_tok"
+    cache = tok.__dict__.get(key)
+    if not isinstance(cache, dict):
+        cache = tok.__dict__[key] = {}
+    wt, bs = tok.pos_embed.weight, tok.pos_embed.bias
+    if wt.device != xp.device:
+        raise RuntimeError(f"TokenInitializer: parameters are on {wt.device} but the input is on {xp.device}")
+    replica = bool(getattr(tok, "_is_replica", False))
+    sig = (float(wt.detach().float().sum()), float(bs.detach().float().sum())) if replica else \
+        (wt.data_ptr(), wt._version, bs.data_ptr(), bs._version)
+    st = cache.get(str(xp.device))
+    if st is None or st[0] != sig:
+        w = wt.detach().float().reshape(-1, 9).contiguous()
+        b = bs.detach().float().contiguous()
+        st = cache[str(xp.device)] = (sig, w, b)
+    return st[1], st[2]
+
+
+def token_geometry(Hp: int, Wp: int, ws: int, cw: int):
+    """Pooling of the detection backbone's TokenInitializer for a padded (Hp, Wp) map (DINO fastervit.py:569-586): per axis
+    out = int(cw * size / ws), stride = int(size / out), kernel = size - (out - 1) * stride; the pooled map is zero-padded to a multiple
+    of cw.  Returns (kh, kw, sh, sw, Ho, Wo, Hq, Wq); the carrier grid is Hq x Wq, G = Hq * Wq."""
+    ks, ss, outs = [], [], []
+    for r in (Hp, Wp):
+        o = int(cw * r / ws)
+        if o < 1:
+            raise ValueError(f"TokenInitializer: a {r}-pixel side gives no carrier token (window {ws}, ct_size {cw})")
+        s = int(r / o)
+        k = r - (o - 1) * s
+        ks.append(k)
+        ss.append(s)
+        outs.append((r - k) // s + 1)
+    Hq, Wq = (_rup(o, cw) for o in outs)
+    return ks[0], ks[1], ss[0], ss[1], outs[0], outs[1], Hq, Wq
+
+
+def token_init_dyn(tok, xp: torch.Tensor, ws: int) -> torch.Tensor:
+    """TokenInitializer.forward of the detection backbone (DINO fastervit.py:569-592) through fvit_token_init_dyn: depthwise conv + bias,
+    average pool with the kernel / stride of THIS map size, zero pad to a multiple of ct_size and the raw NCHW -> (B, G, C) reshape, in one
+    HIP kernel.  ``xp``: the (B, C, Hp, Wp) window-padded map; returns f32 (B, G, C)."""
+    _require_gpu(xp, "TokenInitializer")
+    with torch.no_grad(), torch.cuda.device(xp.device):
+        w, b = _token_weights(tok, xp)
+        B, Cc, Hp, Wp = xp.shape
+        cw = tok.window_size
+        kh, kw, sh, sw, _, _, Hq, Wq = token_geometry(Hp, Wp, ws, cw)
+        ct = torch.empty((B, Hq * Wq, Cc), dtype=torch.float32, device=xp.device)
+        rc = _lib.lib().fvit_token_init_dyn(C.byref(_map_view(xp)), w.data_ptr(), b.data_ptr(), ct.data_ptr(), B, Cc, Hp, Wp, kh, kw, sh, sw,
+                                            cw, _stream_ptr(xp.device))
+        _lib.check(rc, "fvit_token_init_dyn")
+        return ct
+
+
+def _folded_bn(bn, device):
+    """(scale, shift) f32 of an eval BatchNorm2d on ``device``, cached per weight / statistics version."""
+    if bn.running_mean is None or bn.running_var is None:
+        raise NotImplementedError("feature_tap: the BatchNorm2d has no running statistics (track_running_stats=False)")
+    ts = [t for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var) if t is not None]
+    if any(t.device != device for t in ts):
+        raise RuntimeError(f"feature_tap: BatchNorm2d is on {ts[0].device} but the input is on {device}")
+    sig = (str(device),) + tuple((t.data_ptr(), t._version) for t in ts)
+    hit = bn.__dict__.get("_fvit_fold")
+    if hit is None or hit[0] != sig:
+        with torch.no_grad(), torch.autocast(device_type=device.type, enabled=False):
+            scale = torch.rsqrt(bn.running_var.double() + bn.eps)
+            if bn.weight is not None:
+                scale = scale * bn.weight.double()
+            shift = -bn.running_mean.double() * scale
+            if bn.bias is not None:
+                shift = shift + bn.bias.double()
+        hit = (sig, scale.float().contiguous(), shift.float().contiguous())
+        bn.__dict__["_fvit_fold"] = hit
+    return hit[1], hit[2]
+
+
+def feature_tap(x: torch.Tensor, bn, H: Optional[int] = None, W: Optional[int] = None) -> torch.Tensor:
+    """One backbone output level through fvit_feature_tap: the first H x W pixels of ``x`` (any strides: NCHW, channels_last, a view into a
+    padded map), eval BatchNorm2d ``bn`` folded to a per-channel scale / shift, written as contiguous NCHW f32 -- one pass instead of crop +
+    .contiguous() + BatchNorm2d."""
+    _require_gpu(x, "feature_tap")
+    if x.dim() != 4:
+        raise ValueError(f"feature_tap: expected a (B, C, H, W) map, got {tuple(x.shape)}")
+    B, Cc, Hs, Ws = x.shape
+    H = Hs if H is None else int(H)
+    W = Ws if W is None else int(W)
+    if not (0 < H <= Hs and 0 < W <= Ws) or bn.num_features != Cc:
+        raise ValueError(f"feature_tap: crop {H}x{W} of a {tuple(x.shape)} map with a {bn.num_features}-channel BatchNorm2d")
+    with torch.no_grad(), torch.cuda.device(x.device):
+        scale, shift = _folded_bn(bn, x.device)
+        out = torch.empty((B, Cc, H, W), dtype=torch.float32, device=x.device)
+        rc = _lib.lib().fvit_feature_tap(C.byref(_map_view(x)), B, Cc, H, W, scale.data_ptr(), shift.data_ptr(), out.data_ptr(),
+                                         _stream_ptr(x.device))
+        _lib.check(rc, "fvit_feature_tap")
+        return out
 
 
 _WARNED = set()
@@ -600,7 +750,7 @@ def stage_forward(layer, x: torch.Tensor, tokenizer=None, out: Optional[torch.Te
         st = _state(layer, x.device)
         with st.lock:
             st, tb, ctables, dc = _prepare(layer, x.device, Hp, Wp)
-            wsp = _workspace(st, dc, B, H, W, x.device)
+            wsp = _workspace(st, dc, B, H, W, x.device, bounded=bool(getattr(layer, "dynamic_grid", False)))
             if out is None:
                 out = torch.empty_like(x)  # keeps dtype and memory format (NCHW or channels_last)
             elif out.shape != x.shape or out.dtype != x.dtype or out.device != x.device:

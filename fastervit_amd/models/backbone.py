@@ -1,0 +1,187 @@
+"""Multi-scale FasterViT backbone for dense prediction: the detection variant the reference's DINO results use
+(``downstream/object_detection/dino/models/dino/fastervit.py`` = DET), same builder, constructor arguments and ``state_dict`` layout, on
+the HIP engine of the classifier.
+
+What differs from the classifier (fastervit_amd/models/faster_vit.py) and where it is handled:
+
+* every level returns its PRE-downsample map as well (DET:686-708); ``out_indices`` levels go through ``norm{i}`` (eval BatchNorm2d,
+  folded) in one fused HIP pass per level (``fvit_feature_tap``);
+* the window grid of a hierarchical stage is taken from the padded input of each call, not from ``sr_ratio`` (``dynamic_grid``): the
+  packed weights, gather tables and position tables are cached per geometry in ``fastervit_amd.hat_runtime`` (bounded LRU);
+* TokenInitializer (DET:542-592): pool kernel / stride from the padded map of each call, zero pad to a multiple of ct_size, and the raw
+  NCHW -> (B, G, C) reshape without the classifier's per-window permute (``fvit_token_init_dyn``);
+* position tables (DET:176-203): normalised by (token count) // 2 over an arange(h_g) x arange(w_g) grid -- a rectangular carrier grid
+  (``hat_runtime.grid_pos_table``); the carrier attention bias is padded (G > 16) or cropped (G < 16) to G (DET:118-135).
+
+Left out on purpose: DET's ``forward_raw`` applies ``permute(0, 3, 1, 2)`` to an NCHW map (a bug: it scrambles the axes); here
+``forward_features`` returns the NCHW maps ``forward`` uses.  The model is inference-only: no backward exists for carrier grids above 64
+tokens, so train mode (with a transformer stage) and gradient requests raise.
+"""
+from __future__ import annotations
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from .faster_vit import FasterViTLayer, PatchEmbed
+
+# DET:853-960, the builder's eight configurations
+_BACKBONE_CFGS = {
+    "faster_vit_0_224": dict(depths=[2, 3, 6, 5], num_heads=[2, 4, 8, 16], window_size=[7, 7, 7, 7], dim=64, ct_size=2, in_dim=64,
+                             mlp_ratio=4, drop_path_rate=0.1, hat=[False, False, True, False]),
+    "faster_vit_1_224": dict(depths=[1, 3, 8, 5], num_heads=[2, 4, 8, 16], window_size=[7, 7, 7, 7], dim=80, ct_size=2, in_dim=32,
+                             mlp_ratio=4, drop_path_rate=0.1, hat=[False, False, True, False]),
+    "faster_vit_2_224": dict(depths=[3, 3, 8, 5], num_heads=[2, 4, 8, 16], window_size=[7, 7, 7, 7], dim=96, ct_size=2, in_dim=64,
+                             mlp_ratio=4, drop_path_rate=0.1, hat=[False, False, True, False]),
+    "faster_vit_3_224": dict(depths=[3, 3, 12, 5], num_heads=[2, 4, 8, 16], window_size=[7, 7, 7, 7], dim=128, ct_size=2, in_dim=64,
+                             mlp_ratio=4, drop_path_rate=0.1, layer_scale=1e-5, hat=[False, False, True, False]),
+    "faster_vit_4_224": dict(depths=[3, 3, 12, 5], num_heads=[4, 8, 16, 32], window_size=[7, 7, 7, 7], dim=196, ct_size=2, in_dim=64,
+                             mlp_ratio=4, drop_path_rate=0.1, layer_scale=1e-5, hat=[False, False, True, False]),
+    "faster_vit_4_21k_224": dict(depths=[3, 3, 12, 5], num_heads=[4, 8, 16, 32], window_size=[7, 7, 14, 7], dim=196, ct_size=2, in_dim=64,
+                                 mlp_ratio=4, drop_path_rate=0.1, layer_scale=1e-5, hat=[False, False, False, False]),
+    "faster_vit_4_21k_384": dict(depths=[3, 3, 12, 5], num_heads=[4, 8, 16, 32], window_size=[7, 7, 24, 12], dim=196, ct_size=2, in_dim=64,
+                                 mlp_ratio=4, drop_path_rate=0.1, layer_scale=1e-5, hat=[False, False, False, False]),
+    "faster_vit_4_21k_512": dict(depths=[3, 3, 12, 5], num_heads=[4, 8, 16, 32], window_size=[7, 7, 32, 16], dim=196, ct_size=2, in_dim=64,
+                                 mlp_ratio=4, drop_path_rate=0.1, layer_scale=1e-5, hat=[False, False, False, False]),
+}
+BACKBONE_NAMES = tuple(_BACKBONE_CFGS)
+
+
+class BackboneLayer(FasterViTLayer):
+    """FasterViTLayer of the detection variant (DET:595-708): same modules and keys as the classifier's level; ``forward`` returns
+    ``(downsample(x), x)`` with the pre-downsample map, and a hierarchical stage follows the window grid of each input."""
+
+    dynamic_grid = True   # read by fastervit_amd.hat_runtime
+
+    def forward(self, x):
+        if self.transformer_block and len(self.blocks):
+            from .. import hat_runtime
+            tok = None
+            if self.do_gt and self.blocks[0].do_sr_hat:
+                tok = lambda xp: hat_runtime.token_init_dyn(self.global_tokenizer, xp, self.window_size)  # noqa: E731
+            x = hat_runtime.stage_forward(self, x, tokenizer=tok)
+        else:
+            # DET:687-704 pads every level to a multiple of its window, the conv levels too (the second conv of a block then reads the
+            # first one's values in the pad, not zeros, along the right / bottom edge), and crops after the blocks
+            H, W = x.shape[2], x.shape[3]
+            ws = self.window_size
+            pad_r, pad_b = (ws - W % ws) % ws, (ws - H % ws) % ws
+            if pad_r or pad_b:
+                x = F.pad(x, (0, pad_r, 0, pad_b))
+            for blk in self.blocks:
+                x, _ = blk(x, None)
+            x = x[:, :, :H, :W]
+        return (x if self.downsample is None else self.downsample(x)), x
+
+
+class FasterViTBackbone(nn.Module):
+    """DET:710-850.  ``forward(tensor_list)`` takes any object with ``.tensors`` (B, 3, H, W) and ``.mask`` (B, H, W) and returns
+    ``{k: type(tensor_list)(feature, mask)}`` for the k-th entry of ``out_indices``; ``forward_features(x)`` returns the tuple of NCHW
+    fp32 maps.  Any H, W: detection batches change size from call to call."""
+
+    def __init__(self, dim, in_dim, depths, ct_size, mlp_ratio, num_heads, window_size=(7, 7, 7, 7), resolution=224, drop_path_rate=0.2,
+                 in_chans=3, num_classes=1000, qkv_bias=True, qk_scale=None, drop_rate=0., attn_drop_rate=0., layer_scale=None,
+                 layer_scale_conv=None, hat=(False, False, True, False), do_propagation=False, norm_layer=nn.BatchNorm2d,
+                 out_indices=(0, 1, 2, 3), frozen_stages=-1, **kwargs):
+        super().__init__()
+        if norm_layer is not nn.BatchNorm2d:
+            raise NotImplementedError("the output norms are folded into fvit_feature_tap as eval BatchNorm2d; other norm layers are not implemented")
+        self.num_levels = len(depths)
+        self.num_features = [int(dim * 2 ** i) for i in range(self.num_levels)]
+        self.num_classes = num_classes
+        self.patch_embed = PatchEmbed(in_chans=in_chans, in_dim=in_dim, dim=dim)
+        n_blocks = sum(depths)
+        dpr = [drop_path_rate * i / max(n_blocks - 1, 1) for i in range(n_blocks)]
+        if hat is None:
+            hat = [True] * len(depths)
+        self.levels = nn.ModuleList()
+        for i in range(len(depths)):
+            r = int(2 ** (-2 - i) * resolution)
+            self.levels.append(BackboneLayer(
+                dim=int(dim * 2 ** i), depth=depths[i], num_heads=num_heads[i], window_size=window_size[i], ct_size=ct_size,
+                mlp_ratio=mlp_ratio, qkv_bias=qkv_bias, qk_scale=qk_scale, conv=(i < 2), drop=drop_rate, attn_drop=attn_drop_rate,
+                drop_path=dpr[sum(depths[:i]):sum(depths[:i + 1])], downsample=(i < 3), layer_scale=layer_scale,
+                layer_scale_conv=layer_scale_conv, input_resolution=[r, r], only_local=not hat[i], do_propagation=do_propagation,
+                any_res=False))
+        self.out_indices = tuple(out_indices)
+        for i in self.out_indices:
+            self.add_module(f"norm{i}", norm_layer(self.num_features[i]))
+        if frozen_stages >= 2:
+            # DET:807-812 reads self.network, which the reference model does not have (AttributeError)
+            raise ValueError(f"frozen_stages={frozen_stages}: only -1, 0 and 1 are supported (the reference fails for >= 2)")
+        self.frozen_stages = frozen_stages
+        self.hat_operand_dtype = "f16"
+        self._freeze_stages()
+
+    def _freeze_stages(self):
+        """DET:801-805: frozen_stages >= 0 puts the stem in eval mode and stops its gradients (0 and 1 behave alike)."""
+        if self.frozen_stages >= 0:
+            self.patch_embed.eval()
+            for p in self.patch_embed.parameters():
+                p.requires_grad = False
+
+    def train(self, mode: bool = True):
+        super().train(mode)
+        self._freeze_stages()
+        return self
+
+    def set_hat_operand_dtype(self, name: str):
+        """Operand mode of the HAT kernels, as ``FasterViT.set_hat_operand_dtype``: 'f16' (default), 'bf16', 'f16x2', 'bf16x2', 'f16x3',
+        'bf16x3'."""
+        from ..hat_runtime import OPERAND_MODES, x3_unsupported_reason
+        if name not in OPERAND_MODES:
+            raise ValueError(f"operand mode must be one of {OPERAND_MODES}")
+        if name.endswith("x3"):
+            for li, lvl in enumerate(self.levels):
+                why = x3_unsupported_reason(lvl) if lvl.transformer_block and len(lvl.blocks) else None
+                if why is not None:
+                    raise NotImplementedError(f"operand mode {name!r}, level {li}: {why}")
+        self.hat_operand_dtype = name
+        for lvl in self.levels:
+            lvl.hat_operand_dtype = name
+            if lvl.transformer_block:
+                for blk in lvl.blocks:
+                    blk.hat_operand_dtype = name
+        return self
+
+    def _check_inference(self, x: torch.Tensor) -> None:
+        if self.training and any(lvl.transformer_block and len(lvl.blocks) for lvl in self.levels):
+            raise RuntimeError("FasterViTBackbone is inference-only: its transformer stages have no backward (carrier grids above 64 tokens); "
+                               "call model.eval()")
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            raise RuntimeError("FasterViTBackbone is inference-only and its outputs carry no gradient: run it under torch.no_grad() "
+                               "(or torch.inference_mode()), or freeze its parameters and detach the input")
+
+    def forward_features(self, x: torch.Tensor):
+        """Tuple of the ``out_indices`` levels' normalised pre-downsample maps, NCHW fp32."""
+        self._check_inference(x)
+        from ..hat_runtime import feature_tap
+        with torch.no_grad():
+            x = self.patch_embed(x)
+            outs = []
+            for idx, level in enumerate(self.levels):
+                x, xo = level(x)
+                if idx in self.out_indices:
+                    outs.append(feature_tap(xo, getattr(self, f"norm{idx}")))
+        return tuple(outs)
+
+    def forward(self, tensor_list):
+        outs = self.forward_features(tensor_list.tensors)
+        m = tensor_list.mask
+        if m is None:
+            raise ValueError("FasterViTBackbone.forward: tensor_list.mask is None")
+        res = {}
+        for idx, out in enumerate(outs):   # DET:839-844: keys count the returned levels, not the level indices
+            mask = F.interpolate(m[None].float(), size=out.shape[-2:]).to(torch.bool)[0]
+            res[idx] = type(tensor_list)(out, mask)
+        return res
+
+
+def build_fastervit(modelname: str, **kw) -> FasterViTBackbone:
+    """DET:853-960: the builder DINO's ``backbone.py`` calls as ``build_fastervit(name, out_indices=..., use_checkpoint=...)``; keyword
+    arguments override the configuration (``use_checkpoint`` and other unknown ones are accepted and ignored)."""
+    if modelname not in _BACKBONE_CFGS:
+        raise ValueError(f"unknown backbone {modelname!r}; choose from {BACKBONE_NAMES}")
+    cfg = dict(_BACKBONE_CFGS[modelname])
+    cfg.update(kw)
+    return FasterViTBackbone(**cfg)

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define FVIT_ABI_VERSION 8
+#define FVIT_ABI_VERSION 9
 
 /* error codes */
 #define FVIT_OK 0
@@ -207,6 +207,21 @@ int fvit_hat_block_forward(const FvitStageDesc* desc, const FvitBlockWeights* bl
 int fvit_token_init(const FvitMapView* in, const float* weight, const float* bias, float* ct_out, int32_t batch, int32_t C,
                     int32_t Hp, int32_t Wp, int32_t pool_kh, int32_t pool_kw, int32_t pool_sh, int32_t pool_sw, int32_t cw,
                     fvit_stream_t stream);
+
+/* TokenInitializer of the multi-scale detection backbone (DINO models/dino/fastervit.py:542-592, fastervit_amd/models/backbone.py):
+ * depthwise 3x3 conv (pad 1, f32 weight [C][3][3] + bias [C]), AvgPool2d((pool_kh, pool_kw), (pool_sh, pool_sw)) with the kernel and stride the
+ * caller derives from the padded map of THIS call, zero padding of the pooled map to a multiple of cw, and the reference's raw reshape of the
+ * NCHW result to (B, Hq*Wq, C) -- no permute: ct_out is the contiguous (B, C, Hq, Wq) pooled map, read as f32 (B, G, C), G = Hq*Wq.
+ * in: (B, C, Hp, Wp), any strides / fp32, fp16, bf16; Hp*Wp <= 16384. */
+int fvit_token_init_dyn(const FvitMapView* in, const float* weight, const float* bias, float* ct_out, int32_t batch, int32_t C,
+                        int32_t Hp, int32_t Wp, int32_t pool_kh, int32_t pool_kw, int32_t pool_sh, int32_t pool_sw, int32_t cw,
+                        fvit_stream_t stream);
+
+/* One backbone output level (fastervit.py:835-838): reads the first H x W pixels of a (B, C, >=H, >=W) stage map through any strides (NCHW,
+ * channels_last, a crop of a padded map), applies the folded eval BatchNorm2d out = x * scale[c] + shift[c] (scale = gamma / sqrt(var + eps),
+ * shift = beta - mean * scale), and writes contiguous NCHW f32 (B, C, H, W). */
+int fvit_feature_tap(const FvitMapView* in, int32_t batch, int32_t C, int32_t H, int32_t W, const float* scale, const float* shift,
+                     float* out, fvit_stream_t stream);
 
 /* window_partition (AR:84-88) / window_reverse (AR:91-94) as standalone ops on f32 token tensors. */
 int fvit_window_partition(const FvitMapView* in, int32_t batch, int32_t C, int32_t Hp, int32_t Wp,
