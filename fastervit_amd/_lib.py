@@ -17,7 +17,7 @@ LIB_PATH = os.path.join(CSRC_DIR, "libfvit_hip_diag.so" if DIAG else "libfvit_hi
 if os.environ.get("FVIT_LIB_PATH"):
     LIB_PATH = os.path.abspath(os.environ["FVIT_LIB_PATH"])
 
-FVIT_ABI_VERSION = 9
+FVIT_ABI_VERSION = 10
 FVIT_F32, FVIT_F16, FVIT_BF16 = 0, 1, 2
 FVIT_TILE_N, FVIT_TILE_K = 128, 64
 FVIT_MASK_BIAS = -30000.0
@@ -37,7 +37,8 @@ EXPORTED_SYMBOLS = (
     "fvit_conv3x3_nhwc", "fvit_conv3x3_nhwc_terms", "fvit_conv3x3_dense_k", "fvit_conv3x3_patch_form", "fvit_conv3x3_nhwc_dense", "fvit_conv3x3_nhwc_px_dense", "fvit_conv3x3_c128_band_supported", "fvit_conv3x3_c128_band", "fvit_stem_conv3x3s2",
     "fvit_stem_fused", "fvit_window_attention_drop", "fvit_bwd_window_attention_drop", "fvit_global_avgpool_cl", "fvit_conv3x3_nhwc_px", "fvit_layernorm2d_px", "fvit_stem_conv3x3s2_px", "fvit_head_logits", "fvit_head_softmax_xent",
     "fvit_head_grad", "fvit_sgd_momentum", "fvit_bwd_blocks", "fvit_bwd_transpose16", "fvit_bwd_scale_cols", "fvit_bwd_gelu", "fvit_bwd_layernorm",
-    "fvit_bwd_colsum_finish", "fvit_bwd_colsum16", "fvit_bwd_window_attention", "fvit_tune", "fvit_prof_enable", "fvit_prof_collect",
+    "fvit_bwd_colsum_finish", "fvit_bwd_colsum16", "fvit_bwd_window_attention", "fvit_bwd_window_attention_long",
+    "fvit_bwd_window_attention_long_workspace", "fvit_tune", "fvit_prof_enable", "fvit_prof_collect",
     "fvit_prof_records", "fvit_prof_kind_name",
 )
 # only in libfvit_hip_diag.so (the same sources with -DFVIT_DIAG; FVIT_DIAG=1 selects it): diagnosis entry points of include/fvit_hip.h's #ifdef FVIT_DIAG
@@ -258,6 +259,10 @@ def _declare(lib):
     lib.fvit_bwd_colsum_finish.argtypes = [vp, i32, i32, vp, i32, i32, vp]
     lib.fvit_bwd_colsum16.restype = C.c_int
     lib.fvit_bwd_colsum16.argtypes = [i32, vp, i32, vp, i32, i32, vp]
+    lib.fvit_bwd_window_attention_long.restype = C.c_int
+    lib.fvit_bwd_window_attention_long.argtypes = [i32, vp, i32, vp, i32, vp, i32, vp, i32, i32, f32, vp, vp, vp, C.c_size_t, i32, i32, i32, i32, vp]
+    lib.fvit_bwd_window_attention_long_workspace.restype = C.c_size_t
+    lib.fvit_bwd_window_attention_long_workspace.argtypes = [i32, i32, i32, i32, i32]
     lib.fvit_bwd_window_attention.restype = C.c_int
     lib.fvit_bwd_window_attention.argtypes = [i32, vp, i32, vp, i32, vp, i32, f32, vp, vp, i32, i32, i32, i32, vp]
     lib.fvit_tune.restype = C.c_int

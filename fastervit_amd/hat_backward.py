@@ -26,6 +26,14 @@ the forward.  Parameter gradients ACCUMULATE into the buffers of ``MlpGrads`` / 
 run on the head_dim padded to 32 / 64 / 96 with zero channels, like the forward path), any C that is a multiple of 16 (a K dimension is zero-padded
 to a multiple of 64), windows / carrier grids of at most 64 tokens -- every reference entrypoint at 224 x 224.  What this is NOT: backward KERNELS
 for the conv side (PyTorch autograd differentiates those modules) or the optimizer / data loop of train.py; there is no CPU path.
+
+Longer sequences (``FasterViT.enable_hat_backward(True, long_sequences=True)``: the 576 / 1024 / 2304-token windows of faster_vit_4_21k_384 / _512 / _768,
+any-res carrier grids above 64 tokens): the sub-block functions take any S.  For S > 64 the attention core is recomputed by the kernel the inference path
+uses for that length -- fvit_window_attention with the dense (heads, S, S) table where ``fvit_attention_dense(S, dpad)``, otherwise
+fvit_window_attention_long with the COMPACT table (heads, (2w-1)^2) (``CompactBias``) -- and differentiated by fvit_bwd_window_attention_long
+(csrc/fvit_attnbwd.hip: tiled, MFMA, no atomics) with the same bias form; ``AttnGrads.bias`` then holds the gradient of that form, and in the compact form
+the host differentiates the compact table (16 * sigmoid(cpb_mlp(relative_coords_table)), FV:276-280), so no (heads, S, S) tensor exists for S > 208.
+S <= 64 stays on fvit_bwd_window_attention: no gradient computed before changes by a bit.  Not covered above 64 tokens: the attn_drop mask.
 """
 from __future__ import annotations
 
@@ -252,9 +260,78 @@ class AttnGrads:
     bias: Optional[torch.Tensor]
 
     @staticmethod
-    def zeros(C_: int, heads: int, S: int, device, with_gamma: bool = True, with_bias: bool = True) -> "AttnGrads":
+    def zeros(C_: int, heads: int, S: int, device, with_gamma: bool = True, with_bias: bool = True, bias_shape=None) -> "AttnGrads":
+        """``bias_shape``: shape of the bias gradient when it is not the dense (heads, S, S) one -- (heads, (2w-1)^2) for a ``CompactBias``."""
         z = lambda *s: torch.zeros(*s, dtype=torch.float32, device=device)   # noqa: E731
-        return AttnGrads(z(3 * C_, C_), z(3 * C_), z(C_, C_), z(C_), z(C_), z(C_), z(C_) if with_gamma else None, z(heads, S, S) if with_bias else None)
+        bshape = tuple(bias_shape) if bias_shape is not None else (heads, S, S)
+        return AttnGrads(z(3 * C_, C_), z(3 * C_), z(C_, C_), z(C_), z(C_), z(C_), z(C_) if with_gamma else None, z(*bshape) if with_bias else None)
+
+
+@dataclass
+class CompactBias:
+    """The relative-position bias of an attention in the form the long-window kernels index arithmetically: ``table`` fp32 (heads, (2w-1)^2) =
+    16 * sigmoid(cpb_mlp(relative_coords_table)) before the relative_position_index gather (``PosEmbMLPSwinv2D.rel_table``), ``w`` the side of the bias
+    window and ``ng`` the number of leading tokens without bias (ng + w^2 == S).  Accepted as ``bias`` by the attention sub-block functions where
+    ``fvit_attention_dense(S, dpad)`` is false; ``AttnGrads.bias`` is then the gradient of ``table``."""
+    table: torch.Tensor
+    w: int
+    ng: int
+
+
+MAX_SHORT_SEQ = 64   # fvit_bwd_window_attention (one workgroup holds a whole (window, head) in LDS); longer: fvit_bwd_window_attention_long
+
+
+class _Core:
+    """Operands of the attention core of one sub-block call: which forward kernel recomputes it, its bias form, and the matching backward."""
+
+    def __init__(self, lib, who: str, bias, heads: int, S: int, dp: int, dev, pmask):
+        self.long = S > MAX_SHORT_SEQ
+        self.dense = bool(lib.fvit_attention_dense(S, dp)) if self.long else True
+        self.rel, self.w, self.ng, self.btab, self.spad = None, 0, 0, None, 0
+        if self.long and pmask is not None:
+            raise RuntimeError(f"{who}: an attn_drop mask on a sequence of {S} tokens (the attention-core backward above {MAX_SHORT_SEQ} tokens has no Dropout mask)")
+        if isinstance(bias, CompactBias):
+            if self.dense:
+                raise RuntimeError(f"{who}: S = {S} at padded head_dim {dp} runs on the dense-table attention kernel; pass the (heads, S, S) bias")
+            if bias.ng < 0 or bias.ng + bias.w * bias.w != S or tuple(bias.table.shape) != (heads, (2 * bias.w - 1) ** 2):
+                raise RuntimeError(f"{who}: compact bias table {tuple(bias.table.shape)} with w = {bias.w}, ng = {bias.ng} does not cover S = {S} tokens of {heads} heads")
+            self.rel = bias.table.detach().to(device=dev, dtype=torch.float32).contiguous()
+            self.w, self.ng = int(bias.w), int(bias.ng)
+            return
+        if not self.dense:
+            if bias is not None:
+                raise RuntimeError(f"{who}: S = {S} at padded head_dim {dp} runs on the long-window attention kernel, which takes the compact bias table "
+                                   "(hat_backward.CompactBias), not a dense (heads, S, S) one")
+            return
+        self.spad = lib.fvit_attention_spad(S)
+        self.btab = torch.zeros(heads, self.spad, self.spad, dtype=torch.float32, device=dev)   # fvit_window_attention always takes a table (mask on padded keys)
+        if bias is not None:
+            self.btab[:, :S, :S] = bias.detach().to(device=dev, dtype=torch.float32)
+        self.btab[:, :, S:] = _lib.FVIT_MASK_BIAS
+
+    def forward(self, lib, code, qkv, Kq, o, Kao, nwin, S, heads, dp, scale, pmask, st):
+        p = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        if self.dense:
+            _lib.check(lib.fvit_window_attention_drop(code, qkv.data_ptr(), Kq, o.data_ptr(), Kao, self.btab.data_ptr(), nwin, S, heads, dp, C.c_float(scale),
+                                                      p(pmask), st), "attention")
+        else:
+            _lib.check(lib.fvit_window_attention_long(code, qkv.data_ptr(), Kq, o.data_ptr(), Kao, p(self.rel), self.w, self.ng, nwin, S, heads, dp,
+                                                      C.c_float(scale), st), "attention (long)")
+
+    def backward(self, lib, code, qkv, Kq, do, Kao, dqkv, dbias, nwin, S, heads, dp, scale, pmask, st):
+        """dqkv from dO; the bias gradient is ADDED into ``dbias`` (dense (heads, S, S) or the compact table's shape), summed over the windows in window order."""
+        p = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        if not self.long:
+            part = torch.empty(nwin * heads * S * S, dtype=torch.float32, device=qkv.device) if dbias is not None else None
+            _lib.check(lib.fvit_bwd_window_attention_drop(code, qkv.data_ptr(), Kq, do.data_ptr(), Kao, p(self.btab), self.spad, C.c_float(scale), dqkv.data_ptr(),
+                                                          p(part), nwin, S, heads, dp, p(pmask), st), "attention_bwd")
+            if dbias is not None:
+                _lib.check(lib.fvit_bwd_colsum_finish(part.data_ptr(), nwin, heads * S * S, dbias.data_ptr(), heads * S * S, 1, st), "dbias")
+            return
+        nbytes = lib.fvit_bwd_window_attention_long_workspace(nwin, S, heads, dp, self.w if (self.rel is not None and dbias is not None) else 0)
+        ws = torch.empty(nbytes // 4, dtype=torch.float32, device=qkv.device)
+        _lib.check(lib.fvit_bwd_window_attention_long(code, qkv.data_ptr(), Kq, do.data_ptr(), Kao, p(self.btab), self.spad, p(self.rel), self.w, self.ng,
+                                                      C.c_float(scale), dqkv.data_ptr(), p(dbias), ws.data_ptr(), nbytes, nwin, S, heads, dp, st), "attention_bwd (long)")
 
 
 def _attn_geometry(C_: int, heads: int):
@@ -269,17 +346,19 @@ def attn_block_backward(x: torch.Tensor, dy: torch.Tensor, ln_w: torch.Tensor, l
                         grads: AttnGrads, eps: float = 1e-5, qk_scale: Optional[float] = None, operand_dtype=torch.float16,
                         row_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Backward of y = x + gamma * proj(softmax(q k^T * scale + bias) v), [q|k|v] = qkv(LayerNorm(x)), per window of S consecutive rows.
-    x, dy: fp32 [nwin * S][C]; bias: fp32 (heads, S, S) or None; head_dim = C / heads <= 96 (the kernels run on the head_dim padded to 32 / 64 / 96, as
-    the forward path does; C a multiple of 16) and S <= 64.  Returns dx; parameter gradients are added into ``grads``.  ``row_scale``: see
-    ``mlp_block_backward`` (FV:690 ``self.drop_path(self.gamma3 * self.attn(...))``).  Kernel sequence as in ``mlp_block_backward`` with
-    fvit_window_attention (recompute) / fvit_bwd_window_attention in the middle."""
+    x, dy: fp32 [nwin * S][C]; bias: fp32 (heads, S, S), a ``CompactBias`` (S > 64 beyond the dense-table attention kernel) or None; head_dim = C / heads <= 96
+    (the kernels run on the head_dim padded to 32 / 64 / 96, as the forward path does; C a multiple of 16), any S >= 1.  Returns dx; parameter gradients are
+    added into ``grads`` (``grads.bias``: the gradient of the bias in the form it was given).  ``row_scale``: see ``mlp_block_backward`` (FV:690
+    ``self.drop_path(self.gamma3 * self.attn(...))``).  Kernel sequence as in ``mlp_block_backward`` with fvit_window_attention (recompute) /
+    fvit_bwd_window_attention in the middle for S <= 64, and for longer sequences fvit_window_attention or fvit_window_attention_long (whichever the
+    inference path runs at that length) / fvit_bwd_window_attention_long; the attn_drop mask of ``row_scale`` is refused above 64 tokens."""
     if not x.is_cuda:
         raise RuntimeError("attn_block_backward runs only on a HIP device (libfvit_hip.so kernels); there is no CPU fallback")
     if operand_dtype not in _CODE:
         raise ValueError("operand_dtype must be torch.float16 or torch.bfloat16")
     M, C_ = x.shape
-    if C_ % 16 or C_ % heads or C_ // heads > 96 or S < 1 or S > 64 or M % S:
-        raise RuntimeError(f"attn_block_backward: C = {C_}, heads = {heads}, S = {S}, rows = {M}: need head_dim <= 96, C % 16 == 0, S <= 64, rows % S == 0")
+    if C_ % 16 or C_ % heads or C_ // heads > 96 or S < 1 or M % S:
+        raise RuntimeError(f"attn_block_backward: C = {C_}, heads = {heads}, S = {S}, rows = {M}: need head_dim <= 96, C % 16 == 0, S >= 1, rows % S == 0")
     for t, name in ((x, "x"), (dy, "dy")):
         if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (M, C_) or t.device != x.device:
             raise RuntimeError(f"attn_block_backward: {name} must be a contiguous fp32 [rows][C] tensor on {x.device}")
@@ -298,11 +377,7 @@ def attn_block_backward(x: torch.Tensor, dy: torch.Tensor, ln_w: torch.Tensor, l
     bq = bq.contiguous()
     Wq, Wp = _pad_rows(wq, dt, Ck), _pad_rows(wp, dt)                           # [pad(C3p)][Ck], [pad(C)][Kao]
     WqT, WpT = _pad_rows(wq.t().contiguous(), dt, Kq), _pad_rows(wp.t().contiguous(), dt, Ck)   # [pad(C)][Kq], [pad(Kao)][Ck]
-    spad = lib.fvit_attention_spad(S)
-    btab = torch.zeros(heads, spad, spad, dtype=torch.float32, device=dev)   # fvit_window_attention always takes a table (mask on padded keys)
-    if bias is not None:
-        btab[:, :S, :S] = f32(bias)
-    btab[:, :, S:] = _lib.FVIT_MASK_BIAS
+    core = _Core(lib, "attn_block_backward", bias, heads, S, dp, dev, _attn_mask(row_scale))
     e16 = lambda r, c: torch.zeros(r, c, dtype=dt, device=dev)   # noqa: E731
     xn, qkv, o, z = e16(Mp, Ck), e16(Mp, Kq), e16(Mp, Kao), e16(Mp, C_)
     dz, do, dqkv = e16(Mp, Ck), e16(Mp, Kao), e16(Mp, Kq)
@@ -310,7 +385,6 @@ def attn_block_backward(x: torch.Tensor, dy: torch.Tensor, ln_w: torch.Tensor, l
     dqkvT = e16(_rup(C3p, 128), Mk)
     blocks = lib.fvit_bwd_blocks(M)
     part = torch.empty(blocks * 2 * max(C3p, C_), dtype=torch.float32, device=dev)
-    dbias_part = torch.empty(nwin * heads * S * S, dtype=torch.float32, device=dev) if grads.bias is not None else None
     dxn = torch.zeros(M, C_, dtype=torch.float32, device=dev)
     dx = torch.empty(M, C_, dtype=torch.float32, device=dev)
     stats = torch.empty(M, 2, dtype=torch.float32, device=dev)
@@ -329,7 +403,7 @@ def attn_block_backward(x: torch.Tensor, dy: torch.Tensor, ln_w: torch.Tensor, l
                                      C.c_float(eps), M, M, C_, st), "layernorm")
         ck(lib.fvit_gemm_bias_act(code, xn.data_ptr(), Ck, Wq.data_ptr(), Ck, bq.data_ptr(), qkv.data_ptr(), Kq, M, C3p, Ck, 0, st), "qkv")
         pmask = _attn_mask(row_scale)
-        ck(lib.fvit_window_attention_drop(code, qkv.data_ptr(), Kq, o.data_ptr(), Kao, p(btab), nwin, S, heads, dp, C.c_float(scale), p(pmask), st), "attention")
+        core.forward(lib, code, qkv, Kq, o, Kao, nwin, S, heads, dp, scale, pmask, st)
         ck(lib.fvit_gemm_bias_act(code, o.data_ptr(), Kao, Wp.data_ptr(), Kao, bp.data_ptr(), z.data_ptr(), C_, M, C_, Kao, 0, st), "proj")
         # ---- gamma, proj bias, dz = gamma * dy ----
         ck(lib.fvit_bwd_scale_cols(code, dyi.data_ptr(), z.data_ptr(), C_, p(g), dz.data_ptr(), Ck, part.data_ptr(), M, C_, st), "scale_cols")
@@ -342,10 +416,7 @@ def attn_block_backward(x: torch.Tensor, dy: torch.Tensor, ln_w: torch.Tensor, l
         ck(lib.fvit_bwd_transpose16(code, o.data_ptr(), Kao, oT.data_ptr(), Mk, M, Kao, st), "O^T")
         ck(lib.fvit_gemm_residual(code, dzT.data_ptr(), Mk, oT.data_ptr(), Mk, None, None, gp_w.data_ptr(), Kao, C_, Kao, Mk, st), "dWproj")
         # ---- attention core ----
-        ck(lib.fvit_bwd_window_attention_drop(code, qkv.data_ptr(), Kq, do.data_ptr(), Kao, p(btab), spad, C.c_float(scale), dqkv.data_ptr(), p(dbias_part),
-                                              nwin, S, heads, dp, p(pmask), st), "attention_bwd")
-        if grads.bias is not None:
-            ck(lib.fvit_bwd_colsum_finish(dbias_part.data_ptr(), nwin, heads * S * S, grads.bias.data_ptr(), heads * S * S, 1, st), "dbias")
+        core.backward(lib, code, qkv, Kq, do, Kao, dqkv, grads.bias, nwin, S, heads, dp, scale, pmask, st)
         # ---- qkv: bias, dWqkv += dqkv^T xn, dxn = dqkv Wqkv ----
         ck(lib.fvit_bwd_colsum16(code, dqkv.data_ptr(), Kq, part.data_ptr(), M, C3p, st), "colsum dqkv")
         ck(lib.fvit_bwd_colsum_finish(part.data_ptr(), blocks, C3p, gq_b.data_ptr(), C3p, 1, st), "dbqkv")
@@ -389,11 +460,7 @@ def attn_block_forward(x: torch.Tensor, ln_w, ln_b, qkv_w, qkv_b, proj_w, proj_b
     wq, bq = _pack_qkv(f32(qkv_w), f32(qkv_b) if qkv_b is not None else torch.zeros(3 * C_, device=dev), heads, d, dp)
     bq = bq.contiguous()
     Wq, Wp = _pad_rows(wq, dt, Ck), _pad_rows(_pack_proj(f32(proj_w), heads, d, dp, Kao), dt)
-    spad = lib.fvit_attention_spad(S)
-    btab = torch.zeros(heads, spad, spad, dtype=torch.float32, device=dev)
-    if bias is not None:
-        btab[:, :S, :S] = f32(bias)
-    btab[:, :, S:] = _lib.FVIT_MASK_BIAS
+    core = _Core(lib, "attn_block_forward", bias, heads, S, dp, dev, _attn_mask(row_scale))
     xn, qkv, o = (torch.zeros(Mp, n, dtype=dt, device=dev) for n in (Ck, Kq, Kao))
     y = x.clone()
     lw, lb, bp = f32(ln_w), f32(ln_b), f32(proj_b)
@@ -405,8 +472,7 @@ def attn_block_forward(x: torch.Tensor, ln_w, ln_b, qkv_w, qkv_b, proj_w, proj_b
                                      C.c_float(eps), M, M, C_, st), "layernorm")
         ck(lib.fvit_gemm_bias_act(code, xn.data_ptr(), Ck, Wq.data_ptr(), Ck, bq.data_ptr(), qkv.data_ptr(), Kq, M, C3p, Ck, 0, st), "qkv")
         pm = _attn_mask(row_scale)
-        ck(lib.fvit_window_attention_drop(code, qkv.data_ptr(), Kq, o.data_ptr(), Kao, btab.data_ptr(), nwin, S, heads, dp, C.c_float(scale),
-                                          None if pm is None else pm.data_ptr(), st), "attention")
+        core.forward(lib, code, qkv, Kq, o, Kao, nwin, S, heads, dp, scale, pm, st)
         ck(lib.fvit_gemm_residual(code, o.data_ptr(), Kao, Wp.data_ptr(), Kao, bp.data_ptr(), None if g is None else g.data_ptr(), y.data_ptr(), C_,
                                   M, C_, Kao, st), "proj")
     return _lerp_rows(x, y, row_scale)
@@ -697,11 +763,33 @@ def _gm(v):
     return v if isinstance(v, torch.Tensor) else None
 
 
+def _long_enabled(layer) -> bool:
+    return bool(layer.__dict__.get("hat_backward_long", False))
+
+
+def _bias_with_grad(attn, S: int):
+    """The relative-position bias of ``attn`` over S tokens, differentiable w.r.t. its cpb_mlp, in the form the attention core takes at this length:
+    (autograd output, ``bias`` argument of the sub-block functions).  Up to 64 tokens and wherever the inference path uses the dense-table kernel: the folded
+    (heads, S, S) table.  Otherwise the COMPACT table (heads, (2w-1)^2) before the index gather (FV:276-280) with the first S - w^2 tokens carrying no bias
+    (carrier tokens of a window; the zero-padded part of a non-square carrier grid, FV:282-299): no (heads, S, S) autograd graph exists for those lengths."""
+    mod = attn.pos_emb_funct
+    if S <= MAX_SHORT_SEQ or _lib.lib().fvit_attention_dense(S, _dpad(attn.qkv.in_features // attn.num_heads)):
+        t = _table_with_grad(mod, S)
+        return t, t.detach()
+    fn = type(mod).rel_table
+    fn = getattr(fn, "__wrapped__", fn)
+    with torch.enable_grad():
+        t, w = fn(mod)
+    if S - w * w < 0:
+        raise RuntimeError(f"bias window {w}x{w} larger than the sequence ({S} tokens)")
+    return t, CompactBias(t.detach(), int(w), S - w * w)
+
+
 def _local_params(blk, S):
-    bias_t = _table_with_grad(blk.attn.pos_emb_funct, S)   # (heads, S, S), differentiable w.r.t. cpb_mlp
+    bias_t, bias_arg = _bias_with_grad(blk.attn, S)        # dense (heads, S, S) or compact (heads, (2w-1)^2), differentiable w.r.t. cpb_mlp
     pe_t = _table_with_grad(blk.pos_embed)                 # (S, C)
     a = dict(ln_w=blk.norm1.weight, ln_b=blk.norm1.bias, qkv_w=blk.attn.qkv.weight, qkv_b=blk.attn.qkv.bias, proj_w=blk.attn.proj.weight,
-             proj_b=blk.attn.proj.bias, gamma=_gm(blk.gamma3), bias=bias_t.detach(), scale=float(blk.attn.scale))
+             proj_b=blk.attn.proj.bias, gamma=_gm(blk.gamma3), bias=bias_arg, scale=float(blk.attn.scale))
     m = dict(ln_w=blk.norm2.weight, ln_b=blk.norm2.bias, fc1_w=blk.mlp.fc1.weight, fc1_b=blk.mlp.fc1.bias, fc2_w=blk.mlp.fc2.weight, fc2_b=blk.mlp.fc2.bias,
              gamma=_gm(blk.gamma4))
     return a, m, bias_t, pe_t
@@ -716,7 +804,7 @@ def _local_stage_run(layer, x: torch.Tensor, operand_dtype, masks=None):
     ws = blocks[0].window_size
     xp, Hp, Wp = _pad_map(x.float(), ws)                  # F.pad of AR:851-853 (zeros); the output is cropped back (AR:866-867)
     heads, S = blocks[0].attn.num_heads, ws * ws
-    if S > 64:
+    if S > 64 and not _long_enabled(layer):
         raise RuntimeError(f"local stage: windows of {S} tokens (the attention-core backward holds at most 64)")
     nh, nw = Hp // ws, Wp // ws
 
@@ -762,7 +850,7 @@ def local_stage_backward(layer, x: torch.Tensor, dy: torch.Tensor, operand_dtype
     d = partition(dyp)
     for bi in range(len(blocks) - 1, -1, -1):
         blk, xin, (a, m, bias_t, pe_t) = blocks[bi], ins[bi], ps[bi]
-        ag = AttnGrads.zeros(C_, heads, S, x.device, with_gamma=a["gamma"] is not None)
+        ag = AttnGrads.zeros(C_, heads, S, x.device, with_gamma=a["gamma"] is not None, bias_shape=bias_t.shape)
         mg = MlpGrads.zeros(C_, m["fc1_w"].shape[0], x.device, with_gamma=m["gamma"] is not None)
         d = local_block_backward(xin, d, a, m, heads, S, ag, mg, 1e-5, operand_dtype, masks[bi] if masks is not None else None)
         for prm, g in ((blk.norm1.weight, ag.ln_w), (blk.norm1.bias, ag.ln_b), (blk.attn.qkv.weight, ag.qkv_w), (blk.attn.qkv.bias, ag.qkv_b),
@@ -777,13 +865,14 @@ def local_stage_backward(layer, x: torch.Tensor, dy: torch.Tensor, operand_dtype
 
 
 def _hier_params(blk, S, G):
-    t = dict(bias=_table_with_grad(blk.attn.pos_emb_funct, S), hat_bias=_table_with_grad(blk.hat_attn.pos_emb_funct, G), pe_x=_table_with_grad(blk.pos_embed),
+    (bias_t, bias_arg), (hat_t, hat_arg) = _bias_with_grad(blk.attn, S), _bias_with_grad(blk.hat_attn, G)
+    t = dict(bias=bias_t, hat_bias=hat_t, pe_x=_table_with_grad(blk.pos_embed),
              pe_ct=_table_with_grad(blk.hat_pos_embed) if hasattr(blk, "hat_pos_embed") and blk.square else None)
     mk_a = lambda n, at, g, bias: dict(ln_w=n.weight, ln_b=n.bias, qkv_w=at.qkv.weight, qkv_b=at.qkv.bias, proj_w=at.proj.weight, proj_b=at.proj.bias,   # noqa: E731
-                                       gamma=_gm(g), bias=bias.detach(), scale=float(at.scale))
+                                       gamma=_gm(g), bias=bias, scale=float(at.scale))
     mk_m = lambda n, ml, g: dict(ln_w=n.weight, ln_b=n.bias, fc1_w=ml.fc1.weight, fc1_b=ml.fc1.bias, fc2_w=ml.fc2.weight, fc2_b=ml.fc2.bias, gamma=_gm(g))   # noqa: E731
-    return dict(hat_attn=mk_a(blk.hat_norm1, blk.hat_attn, blk.gamma1, t["hat_bias"]), hat_mlp=mk_m(blk.hat_norm2, blk.hat_mlp, blk.gamma2),
-                attn=mk_a(blk.norm1, blk.attn, blk.gamma3, t["bias"]), mlp=mk_m(blk.norm2, blk.mlp, blk.gamma4)), t
+    return dict(hat_attn=mk_a(blk.hat_norm1, blk.hat_attn, blk.gamma1, hat_arg), hat_mlp=mk_m(blk.hat_norm2, blk.hat_mlp, blk.gamma2),
+                attn=mk_a(blk.norm1, blk.attn, blk.gamma3, bias_arg), mlp=mk_m(blk.norm2, blk.mlp, blk.gamma4)), t
 
 
 def _prop_gamma(blk):
@@ -809,7 +898,7 @@ def _hier_stage_run(layer, x: torch.Tensor, operand_dtype, masks=None):
     heads, nloc, ncw = b0.attn.num_heads, ws * ws, cw * cw
     nh, nw = sr
     G, S = ncw * nh * nw, ncw + nloc
-    if S > 64 or G > 64:
+    if (S > 64 or G > 64) and not _long_enabled(layer):
         raise RuntimeError(f"hier stage: {S} tokens per window / {G} carrier tokens per image (the attention-core backward holds at most 64)")
 
     def partition(t):
@@ -849,9 +938,9 @@ def hier_stage_backward(layer, x: torch.Tensor, dy: torch.Tensor, operand_dtype=
     for bi in range(len(blocks) - 1, -1, -1):
         blk, (xb, ctb), (P, t) = blocks[bi], ckpt[bi], ps[bi]
         hid = P["mlp"]["fc1_w"].shape[0]
-        grads = dict(hat_attn=AttnGrads.zeros(C_, heads, G, x.device, with_gamma=P["hat_attn"]["gamma"] is not None),
+        grads = dict(hat_attn=AttnGrads.zeros(C_, heads, G, x.device, with_gamma=P["hat_attn"]["gamma"] is not None, bias_shape=t["hat_bias"].shape),
                      hat_mlp=MlpGrads.zeros(C_, hid, x.device, with_gamma=P["hat_mlp"]["gamma"] is not None),
-                     attn=AttnGrads.zeros(C_, heads, S, x.device, with_gamma=P["attn"]["gamma"] is not None),
+                     attn=AttnGrads.zeros(C_, heads, S, x.device, with_gamma=P["attn"]["gamma"] is not None, bias_shape=t["bias"].shape),
                      mlp=MlpGrads.zeros(C_, hid, x.device, with_gamma=P["mlp"]["gamma"] is not None))
         pg = _prop_gamma(blk)
         prop_grad = torch.zeros(C_, dtype=torch.float32, device=x.device) if isinstance(pg, torch.Tensor) else None
@@ -923,7 +1012,10 @@ def backward_unsupported_reason(layer, H: Optional[int] = None, W: Optional[int]
     from inside ``loss.backward()`` on the autograd engine's thread after a forward that succeeded.
     Covered: head_dim <= 96 (run padded to 32 / 64 / 96), C a multiple of 16, hidden a multiple of 64, windows and carrier grids of at most 64 tokens,
     maps padded up to a multiple of the window, the last block's carrier propagation -- i.e. every reference entrypoint at its native 224 x 224
-    resolution; not the 384+ / any-res geometries with longer windows."""
+    resolution; not the 384+ / any-res geometries with longer windows.
+    With ``layer.hat_backward_long`` (``FasterViT.enable_hat_backward(True, long_sequences=True)``) windows and carrier grids of ANY length are covered
+    (fvit_bwd_window_attention_long); still refused: head_dim > 96, C % 16, hidden % 64, mixed stages, a map that does not tile a fixed-grid stage, and --
+    in TRAIN mode -- ``attn_drop`` > 0 on a sequence above 64 tokens (the long backward has no Dropout mask on the probabilities)."""
     blocks = list(layer.blocks)
     if not blocks:
         return None
@@ -939,11 +1031,20 @@ def backward_unsupported_reason(layer, H: Optional[int] = None, W: Optional[int]
     if any(bool(b.do_sr_hat) != hier for b in blocks):
         return "mixed hierarchical / local blocks in one stage"
     ncw = b0.cr_window ** 2 if hier else 0
-    if ws * ws + ncw > 64:
+    long = _long_enabled(layer)
+    if ws * ws + ncw > 64 and not long:
         return f"windows of {ws * ws + ncw} tokens (the attention-core backward holds at most 64 in LDS)"
+    if long and layer.training:
+        pd = lambda at: float(getattr(at.attn_drop, "p", 0.0) or 0.0)   # noqa: E731
+        G_ = ncw * b0.sr_ratio[0] * b0.sr_ratio[1] if hier else 0
+        for b in blocks:
+            if ws * ws + ncw > 64 and pd(b.attn) > 0:
+                return f"attn_drop = {pd(b.attn)} in train mode on windows of {ws * ws + ncw} tokens (the attention-core backward above 64 tokens has no Dropout mask)"
+            if hier and G_ > 64 and pd(b.hat_attn) > 0:
+                return f"attn_drop = {pd(b.hat_attn)} in train mode on {G_} carrier tokens per image (the attention-core backward above 64 tokens has no Dropout mask)"
     if hier:
         sr = tuple(b0.sr_ratio)
-        if ncw * sr[0] * sr[1] > 64:
+        if ncw * sr[0] * sr[1] > 64 and not long:
             return f"{ncw * sr[0] * sr[1]} carrier tokens per image (at most 64)"
         if H is not None and (-(-H // ws), -(-W // ws)) != sr:
             return f"map {H}x{W} does not pad into the stage's {sr[0]}x{sr[1]} windows of {ws}"

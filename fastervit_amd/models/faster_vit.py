@@ -579,18 +579,28 @@ class FasterViT(nn.Module):
         return PipelinedInference(self, example, depth=depth, streams=streams, dtype=dtype, graph=graph, join_from=join_from, conv_down_terms=conv_down_terms,
                                   precise=precise)
 
-    def enable_hat_backward(self, on: bool = True):
+    def enable_hat_backward(self, on: bool = True, long_sequences: bool = False):
         """Make the transformer stages differentiable in EVAL mode: with grad enabled every HAT stage becomes ONE autograd node whose forward is the HIP
         inference path and whose backward is the kernel sequence of ``fastervit_amd.hat_backward`` (head_dim <= 96, windows and carrier grids of at most
         64 tokens: every entrypoint at 224 x 224; other geometries raise here or -- for a map size that does not fit -- at forward time).  In TRAIN mode
         (``model.train()``) the stages always run as such a node, with stochastic depth (``drop_path_rate``).  The conv stages, norms and head are
-        ordinary PyTorch modules and differentiate as usual.  Off by default: eval mode is inference-only."""
+        ordinary PyTorch modules and differentiate as usual.  Off by default: eval mode is inference-only.
+        ``long_sequences=True`` (opt-in) also covers windows and carrier grids of MORE than 64 tokens -- faster_vit_4_21k_384 / _512 / _768 (one window of
+        576 / 1024 / 2304 tokens), the any-res models on large inputs -- through the tiled MFMA attention backward (fvit_bwd_window_attention_long); the flag
+        is stored on every transformer level (``level.hat_backward_long``) and holds in eval AND train mode.  Still refused, by name and at forward time:
+        head_dim > 96, and ``attn_drop_rate`` > 0 in train mode on such a sequence.  With the default ``False`` nothing changes."""
+        long_on = bool(on and long_sequences)
+        for lvl in self.levels:
+            if lvl.transformer_block:
+                lvl.__dict__["hat_backward_long"] = long_on
         if on:
             from .. import hat_backward
             for i, lvl in enumerate(self.levels):
                 if lvl.transformer_block and len(lvl.blocks):
                     why = hat_backward.backward_unsupported_reason(lvl)
                     if why is not None:
+                        for l2 in self.levels:
+                            l2.__dict__.pop("hat_backward_long", None)
                         raise RuntimeError(f"enable_hat_backward: level {i} of this model has no kernel-sequence backward: {why}")
         self.__dict__["hat_backward"] = bool(on)
         for lvl in self.levels:

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define FVIT_ABI_VERSION 9
+#define FVIT_ABI_VERSION 10
 
 /* error codes */
 #define FVIT_OK 0
@@ -545,6 +545,17 @@ int fvit_bwd_window_attention(int32_t operand_dtype, const void* qkv, int32_t ld
 int fvit_bwd_window_attention_drop(int32_t operand_dtype, const void* qkv, int32_t ld, const void* dO, int32_t ldo, const float* bias, int32_t spad,
                                    float scale, void* dqkv, float* dbias_part, int32_t nwin, int32_t S, int32_t heads, int32_t D, const void* drop_mask,
                                    fvit_stream_t stream);
+/* The same backward for ANY sequence length S >= 1 (csrc/fvit_attnbwd.hip): tiled over queries and keys, the probabilities recomputed per tile from fp32
+ * row statistics, all five products on MFMA, no atomics (bit-reproducible).  Bias form: dense `bias` f32 [heads][spad][spad] (spad >= S) OR the compact
+ * `rel_table` f32 [heads][(2 rel_w - 1)^2] with rel_ng + rel_w^2 == S as fvit_window_attention_long takes it, OR neither (both NULL); giving both is an
+ * error.  dbias (or NULL) ACCUMULATES the bias gradient summed over the windows in window order: dense f32 [heads][S][S] (also with no bias form), compact
+ * f32 [heads][(2 rel_w - 1)^2].  workspace: fvit_bwd_window_attention_long_workspace(nwin, S, heads, D, rel_w of a compact form WITH a bias gradient, else 0)
+ * bytes = 2 * nwin * heads * pad64(S) floats of row statistics + (compact form only) heads * S * S floats: no term grows with nwin * S^2.
+ * ld and ldo must be multiples of 8 elements.  There is no attn_drop mask in this entry point. */
+size_t fvit_bwd_window_attention_long_workspace(int32_t nwin, int32_t S, int32_t heads, int32_t D, int32_t rel_w);
+int fvit_bwd_window_attention_long(int32_t operand_dtype, const void* qkv, int32_t ld, const void* dO, int32_t ldo, const float* bias, int32_t spad,
+                                   const float* rel_table, int32_t rel_w, int32_t rel_ng, float scale, void* dqkv, float* dbias, void* workspace,
+                                   size_t workspace_bytes, int32_t nwin, int32_t S, int32_t heads, int32_t D, fvit_stream_t stream);
 /* out[i] (+)= sum over b < blocks of part[b * stride + i], i < n, in block order. */
 int fvit_bwd_colsum_finish(const float* part, int32_t blocks, int32_t stride, float* out, int32_t n, int32_t accumulate, fvit_stream_t stream);
 
