@@ -134,37 +134,133 @@ class _RS:
         self.rows, self.out, self.hid, self.attn = rows, out, hid, attn
 
 
-def _rows(scale, group: int, out=None, hid=None, attn=None):
-    """Per-group DropPath factors (one per window / per image) -> one per row; with Dropout masks an ``_RS``."""
-    rows = None if scale is None else scale.repeat_interleave(group)
-    if out is None and hid is None and attn is None:
-        return rows
-    return _RS(rows, out, hid, attn)
-
-
-def _rs(mk: Optional[dict], key: str, group: int):
+def _rs(mk: Optional[dict], key: str, group: int) -> _RS:
+    """Sub-block ``key`` of one block's ``drop_path_masks`` entry: per-group DropPath factors (one per window / per image) -> one per row, plus its Dropout masks."""
     mk = mk or {}
-    return _rows(mk.get(key), group, mk.get(key + "_out"), mk.get(key + "_hid"), mk.get(key + "_p"))
+    scale = mk.get(key)
+    return _RS(None if scale is None else scale.repeat_interleave(group), mk.get(key + "_out"), mk.get(key + "_hid"), mk.get(key + "_p"))
 
 
-def _attn_mask(rs):
-    return rs.attn if isinstance(rs, _RS) else None
-
-
-def _out_scale(rs, M: int) -> Optional[torch.Tensor]:
+def _out_scale(rs: _RS, M: int) -> Optional[torch.Tensor]:
     """fp32 factor of the sub-block's output, broadcastable to [M][C] (None: 1)."""
-    if rs is None:
-        return None
-    if isinstance(rs, torch.Tensor):
-        return rs.float().view(M, 1)
     sc = None if rs.rows is None else rs.rows.float().view(M, 1)
     if rs.out is not None:
         sc = rs.out.float() if sc is None else sc * rs.out.float()
     return sc
 
 
-def _hid_mask(rs):
-    return rs.hid if isinstance(rs, _RS) else None
+def _lerp_rows(x: torch.Tensor, y0: torch.Tensor, rs: _RS) -> torch.Tensor:
+    """Stochastic depth on top of the residual epilogue: y0 = x + f  ->  x + row_scale[m] * f."""
+    sc = _out_scale(rs, x.shape[0])
+    if sc is None:
+        return y0
+    return torch.addcmul(x, y0 - x, sc.to(x.dtype).expand_as(x))
+
+
+def _f32(t: torch.Tensor, dev) -> torch.Tensor:
+    return t.detach().to(device=dev, dtype=torch.float32).contiguous()
+
+
+def _p(t: Optional[torch.Tensor]):
+    return None if t is None else t.data_ptr()
+
+
+def _require_hip(who: str, x: torch.Tensor) -> None:
+    if not x.is_cuda:
+        raise RuntimeError(f"{who} runs only on a HIP device (libfvit_hip.so kernels); there is no CPU fallback")
+
+
+def _check_rows(who: str, rows: str, x: torch.Tensor, dy: torch.Tensor) -> None:
+    for t, name in ((x, "x"), (dy, "dy")):
+        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != tuple(x.shape) or t.device != x.device:
+            raise RuntimeError(f"{who}: {name} must be a contiguous fp32 [{rows}][C] tensor on {x.device}")
+
+
+class _Sub:
+    """One sub-block call y = x + gamma * (act W2^T + b2), act = middle(LayerNorm(x) W1^T + b1) -- the steps below are what the MLP and the attention
+    sub-block share: library, operand type, stream, the rows ``x`` with their padded sizes (Ck: C as a GEMM K dimension, zero columns beyond C: FasterViT-4's
+    784 / 1568), the fp32 LayerNorm / gamma parameters, the row scale and, with ``part_cols`` (the widest column sum of a backward), the per-64-row partial
+    sums ``part``.  Every step of a backward finishes its sums from ``part`` before the next step overwrites it: the order of the steps is fixed."""
+
+    def __init__(self, x, ln_w, ln_b, gamma, eps, operand_dtype, row_scale, part_cols: int = 0):
+        self.lib, self.code, self.dt, self.dev, self.x, self.eps = _lib.lib(), _CODE[operand_dtype], operand_dtype, x.device, x, eps
+        self.M, self.C_ = M, C_ = x.shape
+        self.Mp, self.Mk, self.Ck = _rup(M, 128), _rup(M, 64), _rup(C_, 64)
+        self.ln_w, self.ln_b, self.g = _f32(ln_w, x.device), _f32(ln_b, x.device), _f32(gamma, x.device) if gamma is not None else None
+        self.rs = row_scale if isinstance(row_scale, _RS) else _RS(rows=row_scale)   # None, fp32 [M] DropPath factors or an _RS: one internal form
+        self.blocks = self.lib.fvit_bwd_blocks(M)
+        self.part = torch.empty(self.blocks * 2 * part_cols, dtype=torch.float32, device=x.device) if part_cols else None
+        self.st = torch.cuda.current_stream(x.device).cuda_stream
+
+    def z16(self, r: int, c: int) -> torch.Tensor:
+        return torch.zeros(r, c, dtype=self.dt, device=self.dev)
+
+
+def _recompute(k: _Sub, w: torch.Tensor, b: torch.Tensor, n: int, ldn: int, act: int, name: str):
+    """xn = LayerNorm(x) and the first Linear, out[:, :n] = xn w^T + b (``act`` 1: with GELU), as 16-bit rows of stride Ck / ``ldn``."""
+    xn, out = k.z16(k.Mp, k.Ck), k.z16(k.Mp, ldn)
+    W = _pad_rows(w, k.dt, k.Ck)
+    _lib.check(k.lib.fvit_gather_layernorm(k.code, k.x.data_ptr(), k.M, None, 0, None, None, None, None, xn.data_ptr(), k.Ck, k.ln_w.data_ptr(), k.ln_b.data_ptr(),
+                                           C.c_float(k.eps), k.M, k.M, k.C_, k.st), "layernorm")
+    _lib.check(k.lib.fvit_gemm_bias_act(k.code, xn.data_ptr(), k.Ck, W.data_ptr(), k.Ck, b.data_ptr(), out.data_ptr(), ldn, k.M, n, k.Ck, act, k.st), name)
+    return xn, out
+
+
+def _residual_out(k: _Sub, act: torch.Tensor, lda: int, w: torch.Tensor, b: torch.Tensor, name: str) -> torch.Tensor:
+    """The forward's second Linear with the residual epilogue, then stochastic depth: y = x + row_scale * gamma * (act w^T + b)."""
+    W = _pad_rows(w, k.dt)
+    y = k.x.clone()
+    _lib.check(k.lib.fvit_gemm_residual(k.code, act.data_ptr(), lda, W.data_ptr(), lda, b.data_ptr(), _p(k.g), y.data_ptr(), k.C_, k.M, k.C_, lda, k.st), name)
+    return _lerp_rows(k.x, y, k.rs)
+
+
+def _linear_backward(k: _Sub, dout: torch.Tensor, ldo: int, n: int, act: torch.Tensor, lda: int, ka: int, w: torch.Tensor, gw: torch.Tensor, names,
+                     narrow: bool) -> torch.Tensor:
+    """Backward of out[:, :n] = act[:, :ka] w^T from the 16-bit ``dout`` (row stride ``ldo``): gw (n, ka) += dout^T act (two transposes and a GEMM that
+    accumulates in fp32 INTO ``gw``) and the input gradient dout w (weight operand = w^T) -- ``narrow``: 16-bit rows of stride ``lda`` written BEFORE the
+    weight gradient (the second Linear), else fp32 [M][C] accumulated into zeros AFTER it (the first Linear).  ``names`` = (input gradient, dout^T, act^T, gw)."""
+    lib, code, M, Mk, st, ck = k.lib, k.code, k.M, k.Mk, k.st, _lib.check
+    WT = _pad_rows(w.t().contiguous(), k.dt, ldo)
+    doutT, actT = k.z16(_rup(n, 128), Mk), k.z16(_rup(ka, 128), Mk)
+    if narrow:
+        dact = k.z16(k.Mp, lda)
+        ck(lib.fvit_gemm_bias_act(code, dout.data_ptr(), ldo, WT.data_ptr(), ldo, None, dact.data_ptr(), lda, M, ka, ldo, 0, st), names[0])
+    ck(lib.fvit_bwd_transpose16(code, dout.data_ptr(), ldo, doutT.data_ptr(), Mk, M, n, st), names[1])
+    ck(lib.fvit_bwd_transpose16(code, act.data_ptr(), lda, actT.data_ptr(), Mk, M, ka, st), names[2])
+    ck(lib.fvit_gemm_residual(code, doutT.data_ptr(), Mk, actT.data_ptr(), Mk, None, None, gw.data_ptr(), ka, n, ka, Mk, st), names[3])
+    if not narrow:
+        dact = torch.zeros(M, ka, dtype=torch.float32, device=k.dev)
+        ck(lib.fvit_gemm_residual(code, dout.data_ptr(), ldo, WT.data_ptr(), ldo, None, None, dact.data_ptr(), ka, M, ka, ldo, st), names[0])
+    return dact
+
+
+def _output_backward(k: _Sub, dy: torch.Tensor, act: torch.Tensor, lda: int, w: torch.Tensor, b: torch.Tensor, g_gamma, g_b: torch.Tensor, g_w: torch.Tensor,
+                     names) -> torch.Tensor:
+    """From dy back through y = x + row_scale * gamma * z, z = act w^T + b: recompute z, dz = gamma * (what the sub-block sees of dy), the gamma and bias
+    gradients (column sums of dy * z and dz), then the Linear.  Returns d act (16-bit).  ``names`` = (z, bias gradient, d act, act^T, weight gradient)."""
+    lib, code, M, C_, st, ck = k.lib, k.code, k.M, k.C_, k.st, _lib.check
+    W = _pad_rows(w, k.dt)
+    z, dz = k.z16(k.Mp, C_), k.z16(k.Mp, k.Ck)
+    osc = _out_scale(k.rs, M)
+    dyi = dy if osc is None else (dy * osc).contiguous()   # the sub-block sees dy * row_scale, the skip connection sees dy
+    ck(lib.fvit_gemm_bias_act(code, act.data_ptr(), lda, W.data_ptr(), lda, b.data_ptr(), z.data_ptr(), C_, M, C_, lda, 0, st), names[0])
+    ck(lib.fvit_bwd_scale_cols(code, dyi.data_ptr(), z.data_ptr(), C_, _p(k.g), dz.data_ptr(), k.Ck, k.part.data_ptr(), M, C_, st), "scale_cols")
+    if g_gamma is not None:
+        ck(lib.fvit_bwd_colsum_finish(k.part.data_ptr(), k.blocks, 2 * C_, g_gamma.data_ptr(), C_, 1, st), "dgamma")
+    ck(lib.fvit_bwd_colsum_finish(k.part.data_ptr() + 4 * C_, k.blocks, 2 * C_, g_b.data_ptr(), C_, 1, st), names[1])
+    return _linear_backward(k, dz, k.Ck, C_, act, lda, lda, w, g_w, (names[2], "dz^T", names[3], names[4]), narrow=True)
+
+
+def _layernorm_backward(k: _Sub, dxn: torch.Tensor, dy: torch.Tensor, grads) -> torch.Tensor:
+    """dx = dy + LN'(dxn); column sums into grads.ln_w / grads.ln_b."""
+    lib, M, C_, st, ck = k.lib, k.M, k.C_, k.st, _lib.check
+    dx = torch.empty(M, C_, dtype=torch.float32, device=k.dev)
+    stats = torch.empty(M, 2, dtype=torch.float32, device=k.dev)
+    ck(lib.fvit_bwd_layernorm(k.x.data_ptr(), dxn.data_ptr(), dy.data_ptr(), k.ln_w.data_ptr(), C.c_float(k.eps), dx.data_ptr(), stats.data_ptr(),
+                              k.part.data_ptr(), M, C_, st), "layernorm_bwd")
+    ck(lib.fvit_bwd_colsum_finish(k.part.data_ptr(), k.blocks, 2 * C_, grads.ln_w.data_ptr(), C_, 1, st), "dln_w")
+    ck(lib.fvit_bwd_colsum_finish(k.part.data_ptr() + 4 * C_, k.blocks, 2 * C_, grads.ln_b.data_ptr(), C_, 1, st), "dln_b")
+    return dx
 
 
 def mlp_block_backward(x: torch.Tensor, dy: torch.Tensor, ln_w: torch.Tensor, ln_b: torch.Tensor, fc1_w: torch.Tensor, fc1_b: torch.Tensor,
@@ -173,76 +269,45 @@ def mlp_block_backward(x: torch.Tensor, dy: torch.Tensor, ln_w: torch.Tensor, ln
     """Returns dx (fp32 [M][C]) and adds the parameter gradients of the sub-block into ``grads``.  x, dy: fp32 [M][C] on a HIP device.
     ``row_scale`` (fp32 [M], optional): stochastic depth -- y = x + row_scale[m] * gamma * (...) (timm DropPath: 0 or 1 / keep_prob per sample,
     FV:691 ``self.drop_path(self.gamma4 * self.mlp(...))``): the sub-block sees dy * row_scale, the skip connection sees dy."""
-    if not x.is_cuda:
-        raise RuntimeError("mlp_block_backward runs only on a HIP device (libfvit_hip.so kernels); there is no CPU fallback")
+    who = "mlp_block_backward"
+    _require_hip(who, x)
     if operand_dtype not in _CODE:
         raise ValueError("operand_dtype must be torch.float16 or torch.bfloat16")
     M, C_ = x.shape
     hid = fc1_w.shape[0]
     if C_ % 16 or hid % 64:
-        raise RuntimeError(f"mlp_block_backward: C = {C_} must be a multiple of 16 and hidden = {hid} a multiple of 64")
-    for t, name in ((x, "x"), (dy, "dy")):
-        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (M, C_) or t.device != x.device:
-            raise RuntimeError(f"mlp_block_backward: {name} must be a contiguous fp32 [M][C] tensor on {x.device}")
-    dev, dt, code = x.device, operand_dtype, _CODE[operand_dtype]
-    lib = _lib.lib()
-    Mp, Mk, Ck = _rup(M, 128), _rup(M, 64), _rup(C_, 64)   # Ck: C as a GEMM K dimension (zero columns beyond C: FasterViT-4's 784 / 1568)
-    f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()   # noqa: E731
-    ln_w, ln_b, b1, b2 = f32(ln_w), f32(ln_b), f32(fc1_b), f32(fc2_b)
-    g = f32(gamma) if gamma is not None else None
-    w1, w2 = f32(fc1_w), f32(fc2_w)
-    W1, W2 = _pad_rows(w1, dt, Ck), _pad_rows(w2, dt)                  # [pad(hid)][Ck], [pad(C)][hid]
-    W1T, W2T = _pad_rows(w1.t().contiguous(), dt), _pad_rows(w2.t().contiguous(), dt, Ck)   # [pad(C)][hid], [pad(hid)][Ck]
-    e16 = lambda r, c: torch.zeros(r, c, dtype=dt, device=dev)   # noqa: E731
-    xn, a, h, z = e16(Mp, Ck), e16(Mp, hid), e16(Mp, hid), e16(Mp, C_)
-    dz, dh, da = e16(Mp, Ck), e16(Mp, hid), e16(Mp, hid)
-    dzT, xnT = e16(_rup(C_, 128), Mk), e16(_rup(C_, 128), Mk)
-    hT, daT = e16(_rup(hid, 128), Mk), e16(_rup(hid, 128), Mk)
-    blocks = lib.fvit_bwd_blocks(M)
-    part = torch.empty(blocks * 2 * max(C_, hid), dtype=torch.float32, device=dev)
-    dxn = torch.zeros(M, C_, dtype=torch.float32, device=dev)
-    dx = torch.empty(M, C_, dtype=torch.float32, device=dev)
-    stats = torch.empty(M, 2, dtype=torch.float32, device=dev)
-    osc, hmask = _out_scale(row_scale, M), _hid_mask(row_scale)
-    dyi = dy if osc is None else (dy * osc).contiguous()   # what the sub-block sees
-    p = lambda t: None if t is None else t.data_ptr()   # noqa: E731
-    with torch.cuda.device(dev):
-        st = torch.cuda.current_stream(dev).cuda_stream
-        ck = _lib.check
-        # ---- recompute the forward intermediates ----
-        ck(lib.fvit_gather_layernorm(code, x.data_ptr(), M, None, 0, None, None, None, None, xn.data_ptr(), Ck, ln_w.data_ptr(), ln_b.data_ptr(),
-                                     C.c_float(eps), M, M, C_, st), "layernorm")
-        ck(lib.fvit_gemm_bias_act(code, xn.data_ptr(), Ck, W1.data_ptr(), Ck, b1.data_ptr(), a.data_ptr(), hid, M, hid, Ck, 0, st), "fc1")
+        raise RuntimeError(f"{who}: C = {C_} must be a multiple of 16 and hidden = {hid} a multiple of 64")
+    _check_rows(who, "M", x, dy)
+    k = _Sub(x, ln_w, ln_b, gamma, eps, operand_dtype, row_scale, max(C_, hid))
+    with torch.cuda.device(k.dev):
+        lib, code, st, ck = k.lib, k.code, k.st, _lib.check
+        w1, w2, b1, b2 = (_f32(t, k.dev) for t in (fc1_w, fc2_w, fc1_b, fc2_b))
+        xn, a = _recompute(k, w1, b1, hid, hid, 0, "fc1")
+        h, da = k.z16(k.Mp, hid), k.z16(k.Mp, hid)
         ck(lib.fvit_bwd_gelu(code, a.data_ptr(), hid, None, 0, h.data_ptr(), hid, None, M, hid, st), "gelu")
-        if hmask is not None:
-            h[:M] *= hmask          # Dropout on GELU(fc1) (FV:404): the same mask as in the forward
-        ck(lib.fvit_gemm_bias_act(code, h.data_ptr(), hid, W2.data_ptr(), hid, b2.data_ptr(), z.data_ptr(), C_, M, C_, hid, 0, st), "fc2")
-        # ---- gamma, fc2 bias, dz = gamma * dy ----
-        ck(lib.fvit_bwd_scale_cols(code, dyi.data_ptr(), z.data_ptr(), C_, p(g), dz.data_ptr(), Ck, part.data_ptr(), M, C_, st), "scale_cols")
-        if grads.gamma is not None:
-            ck(lib.fvit_bwd_colsum_finish(part.data_ptr(), blocks, 2 * C_, grads.gamma.data_ptr(), C_, 1, st), "dgamma")
-        ck(lib.fvit_bwd_colsum_finish(part.data_ptr() + 4 * C_, blocks, 2 * C_, grads.fc2_b.data_ptr(), C_, 1, st), "db2")
-        # ---- fc2: dh = dz W2, dW2 += dz^T h ----
-        ck(lib.fvit_gemm_bias_act(code, dz.data_ptr(), Ck, W2T.data_ptr(), Ck, None, dh.data_ptr(), hid, M, hid, Ck, 0, st), "dh")
-        ck(lib.fvit_bwd_transpose16(code, dz.data_ptr(), Ck, dzT.data_ptr(), Mk, M, C_, st), "dz^T")
-        ck(lib.fvit_bwd_transpose16(code, h.data_ptr(), hid, hT.data_ptr(), Mk, M, hid, st), "h^T")
-        ck(lib.fvit_gemm_residual(code, dzT.data_ptr(), Mk, hT.data_ptr(), Mk, None, None, grads.fc2_w.data_ptr(), hid, C_, hid, Mk, st), "dW2")
-        # ---- GELU, fc1 bias ----
-        if hmask is not None:
-            dh[:M] *= hmask         # adjoint of the hidden Dropout
-        ck(lib.fvit_bwd_gelu(code, a.data_ptr(), hid, dh.data_ptr(), hid, da.data_ptr(), hid, part.data_ptr(), M, hid, st), "gelu_bwd")
-        ck(lib.fvit_bwd_colsum_finish(part.data_ptr(), blocks, hid, grads.fc1_b.data_ptr(), hid, 1, st), "db1")
-        # ---- fc1: dW1 += da^T xn, dxn = da W1 ----
-        ck(lib.fvit_bwd_transpose16(code, da.data_ptr(), hid, daT.data_ptr(), Mk, M, hid, st), "da^T")
-        ck(lib.fvit_bwd_transpose16(code, xn.data_ptr(), Ck, xnT.data_ptr(), Mk, M, C_, st), "xn^T")
-        ck(lib.fvit_gemm_residual(code, daT.data_ptr(), Mk, xnT.data_ptr(), Mk, None, None, grads.fc1_w.data_ptr(), C_, hid, C_, Mk, st), "dW1")
-        ck(lib.fvit_gemm_residual(code, da.data_ptr(), hid, W1T.data_ptr(), hid, None, None, dxn.data_ptr(), C_, M, C_, hid, st), "dxn")
-        # ---- LayerNorm ----
-        ck(lib.fvit_bwd_layernorm(x.data_ptr(), dxn.data_ptr(), dy.data_ptr(), ln_w.data_ptr(), C.c_float(eps), dx.data_ptr(), stats.data_ptr(),
-                                  part.data_ptr(), M, C_, st), "layernorm_bwd")
-        ck(lib.fvit_bwd_colsum_finish(part.data_ptr(), blocks, 2 * C_, grads.ln_w.data_ptr(), C_, 1, st), "dln_w")
-        ck(lib.fvit_bwd_colsum_finish(part.data_ptr() + 4 * C_, blocks, 2 * C_, grads.ln_b.data_ptr(), C_, 1, st), "dln_b")
-    return dx
+        if k.rs.hid is not None:
+            h[:M] *= k.rs.hid        # Dropout on GELU(fc1) (FV:404): the same mask as in the forward
+        dh = _output_backward(k, dy, h, hid, w2, b2, grads.gamma, grads.fc2_b, grads.fc2_w, ("fc2", "db2", "dh", "h^T", "dW2"))
+        if k.rs.hid is not None:
+            dh[:M] *= k.rs.hid       # adjoint of the hidden Dropout
+        ck(lib.fvit_bwd_gelu(code, a.data_ptr(), hid, dh.data_ptr(), hid, da.data_ptr(), hid, k.part.data_ptr(), M, hid, st), "gelu_bwd")
+        ck(lib.fvit_bwd_colsum_finish(k.part.data_ptr(), k.blocks, hid, grads.fc1_b.data_ptr(), hid, 1, st), "db1")
+        dxn = _linear_backward(k, da, hid, hid, xn, k.Ck, C_, w1, grads.fc1_w, ("dxn", "da^T", "xn^T", "dW1"), narrow=False)
+        return _layernorm_backward(k, dxn, dy, grads)
+
+
+def mlp_block_forward(x: torch.Tensor, ln_w, ln_b, fc1_w, fc1_b, fc2_w, fc2_b, gamma, eps: float = 1e-5, operand_dtype=torch.float16,
+                      row_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y = x + row_scale * gamma * fc2(GELU(fc1(LayerNorm(x)))) through the unit kernels of the forward path (activation recompute for the block-level
+    backwards; train-mode forward with DropPath = ``row_scale``)."""
+    _require_hip("mlp_block_forward", x)
+    hid = fc1_w.shape[0]
+    k = _Sub(x, ln_w, ln_b, gamma, eps, operand_dtype, row_scale)
+    with torch.cuda.device(k.dev):
+        _, h = _recompute(k, _f32(fc1_w, k.dev), _f32(fc1_b, k.dev), hid, hid, 1, "fc1 + GELU")
+        if k.rs.hid is not None:
+            h[:k.M] *= k.rs.hid      # Dropout on GELU(fc1) (FV:404)
+        return _residual_out(k, h, hid, _f32(fc2_w, k.dev), _f32(fc2_b, k.dev), "fc2")
 
 
 @dataclass
@@ -295,7 +360,7 @@ class _Core:
                 raise RuntimeError(f"{who}: S = {S} at padded head_dim {dp} runs on the dense-table attention kernel; pass the (heads, S, S) bias")
             if bias.ng < 0 or bias.ng + bias.w * bias.w != S or tuple(bias.table.shape) != (heads, (2 * bias.w - 1) ** 2):
                 raise RuntimeError(f"{who}: compact bias table {tuple(bias.table.shape)} with w = {bias.w}, ng = {bias.ng} does not cover S = {S} tokens of {heads} heads")
-            self.rel = bias.table.detach().to(device=dev, dtype=torch.float32).contiguous()
+            self.rel = _f32(bias.table, dev)
             self.w, self.ng = int(bias.w), int(bias.ng)
             return
         if not self.dense:
@@ -310,28 +375,26 @@ class _Core:
         self.btab[:, :, S:] = _lib.FVIT_MASK_BIAS
 
     def forward(self, lib, code, qkv, Kq, o, Kao, nwin, S, heads, dp, scale, pmask, st):
-        p = lambda t: None if t is None else t.data_ptr()   # noqa: E731
         if self.dense:
             _lib.check(lib.fvit_window_attention_drop(code, qkv.data_ptr(), Kq, o.data_ptr(), Kao, self.btab.data_ptr(), nwin, S, heads, dp, C.c_float(scale),
-                                                      p(pmask), st), "attention")
+                                                      _p(pmask), st), "attention")
         else:
-            _lib.check(lib.fvit_window_attention_long(code, qkv.data_ptr(), Kq, o.data_ptr(), Kao, p(self.rel), self.w, self.ng, nwin, S, heads, dp,
+            _lib.check(lib.fvit_window_attention_long(code, qkv.data_ptr(), Kq, o.data_ptr(), Kao, _p(self.rel), self.w, self.ng, nwin, S, heads, dp,
                                                       C.c_float(scale), st), "attention (long)")
 
     def backward(self, lib, code, qkv, Kq, do, Kao, dqkv, dbias, nwin, S, heads, dp, scale, pmask, st):
         """dqkv from dO; the bias gradient is ADDED into ``dbias`` (dense (heads, S, S) or the compact table's shape), summed over the windows in window order."""
-        p = lambda t: None if t is None else t.data_ptr()   # noqa: E731
         if not self.long:
             part = torch.empty(nwin * heads * S * S, dtype=torch.float32, device=qkv.device) if dbias is not None else None
-            _lib.check(lib.fvit_bwd_window_attention_drop(code, qkv.data_ptr(), Kq, do.data_ptr(), Kao, p(self.btab), self.spad, C.c_float(scale), dqkv.data_ptr(),
-                                                          p(part), nwin, S, heads, dp, p(pmask), st), "attention_bwd")
+            _lib.check(lib.fvit_bwd_window_attention_drop(code, qkv.data_ptr(), Kq, do.data_ptr(), Kao, _p(self.btab), self.spad, C.c_float(scale), dqkv.data_ptr(),
+                                                          _p(part), nwin, S, heads, dp, _p(pmask), st), "attention_bwd")
             if dbias is not None:
                 _lib.check(lib.fvit_bwd_colsum_finish(part.data_ptr(), nwin, heads * S * S, dbias.data_ptr(), heads * S * S, 1, st), "dbias")
             return
         nbytes = lib.fvit_bwd_window_attention_long_workspace(nwin, S, heads, dp, self.w if (self.rel is not None and dbias is not None) else 0)
         ws = torch.empty(nbytes // 4, dtype=torch.float32, device=qkv.device)
-        _lib.check(lib.fvit_bwd_window_attention_long(code, qkv.data_ptr(), Kq, do.data_ptr(), Kao, p(self.btab), self.spad, p(self.rel), self.w, self.ng,
-                                                      C.c_float(scale), dqkv.data_ptr(), p(dbias), ws.data_ptr(), nbytes, nwin, S, heads, dp, st), "attention_bwd (long)")
+        _lib.check(lib.fvit_bwd_window_attention_long(code, qkv.data_ptr(), Kq, do.data_ptr(), Kao, _p(self.btab), self.spad, _p(self.rel), self.w, self.ng,
+                                                      C.c_float(scale), dqkv.data_ptr(), _p(dbias), ws.data_ptr(), nbytes, nwin, S, heads, dp, st), "attention_bwd (long)")
 
 
 def _attn_geometry(C_: int, heads: int):
@@ -339,6 +402,20 @@ def _attn_geometry(C_: int, heads: int):
     dp = _dpad(d)
     HD = heads * dp
     return d, dp, HD, 3 * HD, _rup(3 * HD, 64), _rup(HD, 64), _rup(C_, 64)
+
+
+def _attn_recompute(k: _Sub, who: str, geo, qkv_w, qkv_b, proj_w, bias, heads: int, S: int, qk_scale):
+    """What both attention functions start from: qkv / proj weights in the padded head layout ([C3p][C], [C][Kao]), the core for this S and bias form, and
+    xn = LayerNorm(x), qkv = xn Wqkv^T + b, o = attention(qkv).  ``run``: the arguments ``_Core.forward`` and ``_Core.backward`` share."""
+    d, dp, _, C3p, Kq, Kao, _ = geo
+    wq, bq = _pack_qkv(_f32(qkv_w, k.dev), _f32(qkv_b, k.dev) if qkv_b is not None else torch.zeros(3 * k.C_, device=k.dev), heads, d, dp)
+    wp = _pack_proj(_f32(proj_w, k.dev), heads, d, dp, Kao)
+    core = _Core(k.lib, who, bias, heads, S, dp, k.dev, k.rs.attn)
+    xn, qkv = _recompute(k, wq, bq.contiguous(), C3p, Kq, 0, "qkv")
+    o = k.z16(k.Mp, Kao)
+    run = (k.M // S, S, heads, dp, float(qk_scale) if qk_scale else d ** -0.5, k.rs.attn, k.st)
+    core.forward(k.lib, k.code, qkv, Kq, o, Kao, *run)
+    return wq, wp, core, xn, qkv, o, run
 
 
 def attn_block_backward(x: torch.Tensor, dy: torch.Tensor, ln_w: torch.Tensor, ln_b: torch.Tensor, qkv_w: torch.Tensor, qkv_b: Optional[torch.Tensor],
@@ -352,83 +429,32 @@ def attn_block_backward(x: torch.Tensor, dy: torch.Tensor, ln_w: torch.Tensor, l
     ``self.drop_path(self.gamma3 * self.attn(...))``).  Kernel sequence as in ``mlp_block_backward`` with fvit_window_attention (recompute) /
     fvit_bwd_window_attention in the middle for S <= 64, and for longer sequences fvit_window_attention or fvit_window_attention_long (whichever the
     inference path runs at that length) / fvit_bwd_window_attention_long; the attn_drop mask of ``row_scale`` is refused above 64 tokens."""
-    if not x.is_cuda:
-        raise RuntimeError("attn_block_backward runs only on a HIP device (libfvit_hip.so kernels); there is no CPU fallback")
+    who = "attn_block_backward"
+    _require_hip(who, x)
     if operand_dtype not in _CODE:
         raise ValueError("operand_dtype must be torch.float16 or torch.bfloat16")
     M, C_ = x.shape
     if C_ % 16 or C_ % heads or C_ // heads > 96 or S < 1 or M % S:
-        raise RuntimeError(f"attn_block_backward: C = {C_}, heads = {heads}, S = {S}, rows = {M}: need head_dim <= 96, C % 16 == 0, S >= 1, rows % S == 0")
-    for t, name in ((x, "x"), (dy, "dy")):
-        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != (M, C_) or t.device != x.device:
-            raise RuntimeError(f"attn_block_backward: {name} must be a contiguous fp32 [rows][C] tensor on {x.device}")
-    dev, dt, code = x.device, operand_dtype, _CODE[operand_dtype]
-    lib = _lib.lib()
-    d, dp, HD, C3p, Kq, Kao, Ck = _attn_geometry(C_, heads)
+        raise RuntimeError(f"{who}: C = {C_}, heads = {heads}, S = {S}, rows = {M}: need head_dim <= 96, C % 16 == 0, S >= 1, rows % S == 0")
+    _check_rows(who, "rows", x, dy)
+    geo = _attn_geometry(C_, heads)
+    d, dp, _, C3p, Kq, Kao, _ = geo
     padded = d != dp or Kao != C_
-    nwin = M // S
-    scale = float(qk_scale) if qk_scale else d ** -0.5
-    Mp, Mk = _rup(M, 128), _rup(M, 64)
-    f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()   # noqa: E731
-    ln_w, ln_b, bp = f32(ln_w), f32(ln_b), f32(proj_b)
-    g = f32(gamma) if gamma is not None else None
-    wq, bq = _pack_qkv(f32(qkv_w), f32(qkv_b) if qkv_b is not None else torch.zeros(3 * C_, device=dev), heads, d, dp)   # [C3p][C], [C3p]
-    wp = _pack_proj(f32(proj_w), heads, d, dp, Kao)                                                                      # [C][Kao]
-    bq = bq.contiguous()
-    Wq, Wp = _pad_rows(wq, dt, Ck), _pad_rows(wp, dt)                           # [pad(C3p)][Ck], [pad(C)][Kao]
-    WqT, WpT = _pad_rows(wq.t().contiguous(), dt, Kq), _pad_rows(wp.t().contiguous(), dt, Ck)   # [pad(C)][Kq], [pad(Kao)][Ck]
-    core = _Core(lib, "attn_block_backward", bias, heads, S, dp, dev, _attn_mask(row_scale))
-    e16 = lambda r, c: torch.zeros(r, c, dtype=dt, device=dev)   # noqa: E731
-    xn, qkv, o, z = e16(Mp, Ck), e16(Mp, Kq), e16(Mp, Kao), e16(Mp, C_)
-    dz, do, dqkv = e16(Mp, Ck), e16(Mp, Kao), e16(Mp, Kq)
-    dzT, oT, xnT = e16(_rup(C_, 128), Mk), e16(_rup(Kao, 128), Mk), e16(_rup(C_, 128), Mk)
-    dqkvT = e16(_rup(C3p, 128), Mk)
-    blocks = lib.fvit_bwd_blocks(M)
-    part = torch.empty(blocks * 2 * max(C3p, C_), dtype=torch.float32, device=dev)
-    dxn = torch.zeros(M, C_, dtype=torch.float32, device=dev)
-    dx = torch.empty(M, C_, dtype=torch.float32, device=dev)
-    stats = torch.empty(M, 2, dtype=torch.float32, device=dev)
-    # gradient buffers in the padded layout (the accumulating GEMMs write straight into ``grads`` when no padding is involved)
-    gq_w = torch.zeros(C3p, C_, dtype=torch.float32, device=dev) if padded else grads.qkv_w
-    gq_b = torch.zeros(C3p, dtype=torch.float32, device=dev) if padded else grads.qkv_b
-    gp_w = torch.zeros(C_, Kao, dtype=torch.float32, device=dev) if padded else grads.proj_w
-    osc = _out_scale(row_scale, M)
-    dyi = dy if osc is None else (dy * osc).contiguous()
-    p = lambda t: None if t is None else t.data_ptr()   # noqa: E731
-    with torch.cuda.device(dev):
-        st = torch.cuda.current_stream(dev).cuda_stream
-        ck = _lib.check
-        # ---- recompute the forward intermediates ----
-        ck(lib.fvit_gather_layernorm(code, x.data_ptr(), M, None, 0, None, None, None, None, xn.data_ptr(), Ck, ln_w.data_ptr(), ln_b.data_ptr(),
-                                     C.c_float(eps), M, M, C_, st), "layernorm")
-        ck(lib.fvit_gemm_bias_act(code, xn.data_ptr(), Ck, Wq.data_ptr(), Ck, bq.data_ptr(), qkv.data_ptr(), Kq, M, C3p, Ck, 0, st), "qkv")
-        pmask = _attn_mask(row_scale)
-        core.forward(lib, code, qkv, Kq, o, Kao, nwin, S, heads, dp, scale, pmask, st)
-        ck(lib.fvit_gemm_bias_act(code, o.data_ptr(), Kao, Wp.data_ptr(), Kao, bp.data_ptr(), z.data_ptr(), C_, M, C_, Kao, 0, st), "proj")
-        # ---- gamma, proj bias, dz = gamma * dy ----
-        ck(lib.fvit_bwd_scale_cols(code, dyi.data_ptr(), z.data_ptr(), C_, p(g), dz.data_ptr(), Ck, part.data_ptr(), M, C_, st), "scale_cols")
-        if grads.gamma is not None:
-            ck(lib.fvit_bwd_colsum_finish(part.data_ptr(), blocks, 2 * C_, grads.gamma.data_ptr(), C_, 1, st), "dgamma")
-        ck(lib.fvit_bwd_colsum_finish(part.data_ptr() + 4 * C_, blocks, 2 * C_, grads.proj_b.data_ptr(), C_, 1, st), "dbproj")
-        # ---- proj: dO = dz Wp, dWp += dz^T O ----
-        ck(lib.fvit_gemm_bias_act(code, dz.data_ptr(), Ck, WpT.data_ptr(), Ck, None, do.data_ptr(), Kao, M, Kao, Ck, 0, st), "dO")
-        ck(lib.fvit_bwd_transpose16(code, dz.data_ptr(), Ck, dzT.data_ptr(), Mk, M, C_, st), "dz^T")
-        ck(lib.fvit_bwd_transpose16(code, o.data_ptr(), Kao, oT.data_ptr(), Mk, M, Kao, st), "O^T")
-        ck(lib.fvit_gemm_residual(code, dzT.data_ptr(), Mk, oT.data_ptr(), Mk, None, None, gp_w.data_ptr(), Kao, C_, Kao, Mk, st), "dWproj")
-        # ---- attention core ----
-        core.backward(lib, code, qkv, Kq, do, Kao, dqkv, grads.bias, nwin, S, heads, dp, scale, pmask, st)
-        # ---- qkv: bias, dWqkv += dqkv^T xn, dxn = dqkv Wqkv ----
-        ck(lib.fvit_bwd_colsum16(code, dqkv.data_ptr(), Kq, part.data_ptr(), M, C3p, st), "colsum dqkv")
-        ck(lib.fvit_bwd_colsum_finish(part.data_ptr(), blocks, C3p, gq_b.data_ptr(), C3p, 1, st), "dbqkv")
-        ck(lib.fvit_bwd_transpose16(code, dqkv.data_ptr(), Kq, dqkvT.data_ptr(), Mk, M, C3p, st), "dqkv^T")
-        ck(lib.fvit_bwd_transpose16(code, xn.data_ptr(), Ck, xnT.data_ptr(), Mk, M, C_, st), "xn^T")
-        ck(lib.fvit_gemm_residual(code, dqkvT.data_ptr(), Mk, xnT.data_ptr(), Mk, None, None, gq_w.data_ptr(), C_, C3p, C_, Mk, st), "dWqkv")
-        ck(lib.fvit_gemm_residual(code, dqkv.data_ptr(), Kq, WqT.data_ptr(), Kq, None, None, dxn.data_ptr(), C_, M, C_, Kq, st), "dxn")
-        # ---- LayerNorm ----
-        ck(lib.fvit_bwd_layernorm(x.data_ptr(), dxn.data_ptr(), dy.data_ptr(), ln_w.data_ptr(), C.c_float(eps), dx.data_ptr(), stats.data_ptr(),
-                                  part.data_ptr(), M, C_, st), "layernorm_bwd")
-        ck(lib.fvit_bwd_colsum_finish(part.data_ptr(), blocks, 2 * C_, grads.ln_w.data_ptr(), C_, 1, st), "dln_w")
-        ck(lib.fvit_bwd_colsum_finish(part.data_ptr() + 4 * C_, blocks, 2 * C_, grads.ln_b.data_ptr(), C_, 1, st), "dln_b")
+    k = _Sub(x, ln_w, ln_b, gamma, eps, operand_dtype, row_scale, max(C3p, C_))
+    with torch.cuda.device(k.dev):
+        lib, code, st, ck = k.lib, k.code, k.st, _lib.check
+        wq, wp, core, xn, qkv, o, run = _attn_recompute(k, who, geo, qkv_w, qkv_b, proj_w, bias, heads, S, qk_scale)
+        # gradient buffers in the padded layout (the accumulating GEMMs write straight into ``grads`` when no padding is involved)
+        gq_w = torch.zeros(C3p, C_, dtype=torch.float32, device=k.dev) if padded else grads.qkv_w
+        gq_b = torch.zeros(C3p, dtype=torch.float32, device=k.dev) if padded else grads.qkv_b
+        gp_w = torch.zeros(C_, Kao, dtype=torch.float32, device=k.dev) if padded else grads.proj_w
+        do = _output_backward(k, dy, o, Kao, wp, _f32(proj_b, k.dev), grads.gamma, grads.proj_b, gp_w, ("proj", "dbproj", "dO", "O^T", "dWproj"))
+        dqkv = k.z16(k.Mp, Kq)
+        core.backward(lib, code, qkv, Kq, do, Kao, dqkv, grads.bias, *run)
+        ck(lib.fvit_bwd_colsum16(code, dqkv.data_ptr(), Kq, k.part.data_ptr(), M, C3p, st), "colsum dqkv")
+        ck(lib.fvit_bwd_colsum_finish(k.part.data_ptr(), k.blocks, C3p, gq_b.data_ptr(), C3p, 1, st), "dbqkv")
+        dxn = _linear_backward(k, dqkv, Kq, C3p, xn, k.Ck, C_, wq, gq_w, ("dxn", "dqkv^T", "xn^T", "dWqkv"), narrow=False)
+        dx = _layernorm_backward(k, dxn, dy, grads)
     if padded:   # the real rows / columns of the padded-layout gradients
         grads.qkv_w += _unpack_qkv(gq_w, heads, d, dp)
         grads.qkv_b += _unpack_qkv(gq_b, heads, d, dp)
@@ -436,46 +462,26 @@ def attn_block_backward(x: torch.Tensor, dy: torch.Tensor, ln_w: torch.Tensor, l
     return dx
 
 
-def _lerp_rows(x: torch.Tensor, y0: torch.Tensor, row_scale: Optional[torch.Tensor]) -> torch.Tensor:
-    """Stochastic depth on top of the residual epilogue: y0 = x + f  ->  x + row_scale[m] * f."""
-    sc = _out_scale(row_scale, x.shape[0])
-    if sc is None:
-        return y0
-    return torch.addcmul(x, y0 - x, sc.to(x.dtype).expand_as(x))
-
-
 def attn_block_forward(x: torch.Tensor, ln_w, ln_b, qkv_w, qkv_b, proj_w, proj_b, gamma, bias, heads: int, S: int, eps: float = 1e-5,
                        qk_scale: Optional[float] = None, operand_dtype=torch.float16, row_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """y = x + row_scale * gamma * proj(attention(qkv(LayerNorm(x)))) through the unit kernels of the forward path (LayerNorm, GEMM, attention core, GEMM
     with the residual epilogue): the activation recompute a block-level backward starts from, and the train-mode forward (DropPath = ``row_scale``)."""
-    if not x.is_cuda:
-        raise RuntimeError("attn_block_forward runs only on a HIP device (libfvit_hip.so kernels); there is no CPU fallback")
-    M, C_ = x.shape
-    dev, dt, code = x.device, operand_dtype, _CODE[operand_dtype]
-    lib = _lib.lib()
-    d, dp, HD, C3p, Kq, Kao, Ck = _attn_geometry(C_, heads)
-    nwin, Mp = M // S, _rup(M, 128)
-    scale = float(qk_scale) if qk_scale else d ** -0.5
-    f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()   # noqa: E731
-    wq, bq = _pack_qkv(f32(qkv_w), f32(qkv_b) if qkv_b is not None else torch.zeros(3 * C_, device=dev), heads, d, dp)
-    bq = bq.contiguous()
-    Wq, Wp = _pad_rows(wq, dt, Ck), _pad_rows(_pack_proj(f32(proj_w), heads, d, dp, Kao), dt)
-    core = _Core(lib, "attn_block_forward", bias, heads, S, dp, dev, _attn_mask(row_scale))
-    xn, qkv, o = (torch.zeros(Mp, n, dtype=dt, device=dev) for n in (Ck, Kq, Kao))
-    y = x.clone()
-    lw, lb, bp = f32(ln_w), f32(ln_b), f32(proj_b)
-    g = f32(gamma) if gamma is not None else None
-    with torch.cuda.device(dev):
-        st = torch.cuda.current_stream(dev).cuda_stream
-        ck = _lib.check
-        ck(lib.fvit_gather_layernorm(code, x.data_ptr(), M, None, 0, None, None, None, None, xn.data_ptr(), Ck, lw.data_ptr(), lb.data_ptr(),
-                                     C.c_float(eps), M, M, C_, st), "layernorm")
-        ck(lib.fvit_gemm_bias_act(code, xn.data_ptr(), Ck, Wq.data_ptr(), Ck, bq.data_ptr(), qkv.data_ptr(), Kq, M, C3p, Ck, 0, st), "qkv")
-        pm = _attn_mask(row_scale)
-        core.forward(lib, code, qkv, Kq, o, Kao, nwin, S, heads, dp, scale, pm, st)
-        ck(lib.fvit_gemm_residual(code, o.data_ptr(), Kao, Wp.data_ptr(), Kao, bp.data_ptr(), None if g is None else g.data_ptr(), y.data_ptr(), C_,
-                                  M, C_, Kao, st), "proj")
-    return _lerp_rows(x, y, row_scale)
+    who = "attn_block_forward"
+    _require_hip(who, x)
+    geo = _attn_geometry(x.shape[1], heads)
+    k = _Sub(x, ln_w, ln_b, gamma, eps, operand_dtype, row_scale)
+    with torch.cuda.device(k.dev):
+        _, wp, _, _, _, o, _ = _attn_recompute(k, who, geo, qkv_w, qkv_b, proj_w, bias, heads, S, qk_scale)
+        return _residual_out(k, o, geo[5], wp, _f32(proj_b, k.dev), "proj")
+
+
+def _attn_args(a: dict):
+    """A sub-block's parameter dict as the leading tensor arguments of ``attn_block_forward`` / ``attn_block_backward`` (after x / x, dy)."""
+    return a["ln_w"], a["ln_b"], a["qkv_w"], a.get("qkv_b"), a["proj_w"], a["proj_b"], a.get("gamma"), a.get("bias")
+
+
+def _mlp_args(m: dict):
+    return m["ln_w"], m["ln_b"], m["fc1_w"], m["fc1_b"], m["fc2_w"], m["fc2_b"], m.get("gamma")
 
 
 def local_block_backward(x: torch.Tensor, dy: torch.Tensor, attn: dict, mlp: dict, heads: int, S: int, attn_grads: AttnGrads, mlp_grads: MlpGrads,
@@ -486,42 +492,9 @@ def local_block_backward(x: torch.Tensor, dy: torch.Tensor, attn: dict, mlp: dic
     ``masks`` = dict(attn=, mlp=) per-WINDOW DropPath factors or None (train mode).  x1 is recomputed by the forward kernels, then the two sub-block
     backwards run in reverse order.  Returns dx."""
     ra, rm = _rs(masks, "attn", S), _rs(masks, "mlp", S)
-    x1 = attn_block_forward(x, attn["ln_w"], attn["ln_b"], attn["qkv_w"], attn.get("qkv_b"), attn["proj_w"], attn["proj_b"], attn.get("gamma"),
-                            attn.get("bias"), heads, S, eps, attn.get("scale"), operand_dtype, ra)
-    dx1 = mlp_block_backward(x1, dy, mlp["ln_w"], mlp["ln_b"], mlp["fc1_w"], mlp["fc1_b"], mlp["fc2_w"], mlp["fc2_b"], mlp.get("gamma"), mlp_grads, eps,
-                             operand_dtype, rm)
-    return attn_block_backward(x, dx1, attn["ln_w"], attn["ln_b"], attn["qkv_w"], attn.get("qkv_b"), attn["proj_w"], attn["proj_b"], attn.get("gamma"),
-                               attn.get("bias"), heads, S, attn_grads, eps, attn.get("scale"), operand_dtype, ra)
-
-
-def mlp_block_forward(x: torch.Tensor, ln_w, ln_b, fc1_w, fc1_b, fc2_w, fc2_b, gamma, eps: float = 1e-5, operand_dtype=torch.float16,
-                      row_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """y = x + row_scale * gamma * fc2(GELU(fc1(LayerNorm(x)))) through the unit kernels of the forward path (activation recompute for the block-level
-    backwards; train-mode forward with DropPath = ``row_scale``)."""
-    if not x.is_cuda:
-        raise RuntimeError("mlp_block_forward runs only on a HIP device (libfvit_hip.so kernels); there is no CPU fallback")
-    M, C_ = x.shape
-    hid = fc1_w.shape[0]
-    dev, dt, code = x.device, operand_dtype, _CODE[operand_dtype]
-    lib = _lib.lib()
-    Mp, Ck = _rup(M, 128), _rup(C_, 64)
-    f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()   # noqa: E731
-    W1, W2 = _pad_rows(f32(fc1_w), dt, Ck), _pad_rows(f32(fc2_w), dt)
-    xn, h = torch.zeros(Mp, Ck, dtype=dt, device=dev), torch.zeros(Mp, hid, dtype=dt, device=dev)
-    y = x.clone()
-    lw, lb, b1, b2 = f32(ln_w), f32(ln_b), f32(fc1_b), f32(fc2_b)
-    g = f32(gamma) if gamma is not None else None
-    with torch.cuda.device(dev):
-        st = torch.cuda.current_stream(dev).cuda_stream
-        ck = _lib.check
-        ck(lib.fvit_gather_layernorm(code, x.data_ptr(), M, None, 0, None, None, None, None, xn.data_ptr(), Ck, lw.data_ptr(), lb.data_ptr(),
-                                     C.c_float(eps), M, M, C_, st), "layernorm")
-        ck(lib.fvit_gemm_bias_act(code, xn.data_ptr(), Ck, W1.data_ptr(), Ck, b1.data_ptr(), h.data_ptr(), hid, M, hid, Ck, 1, st), "fc1 + GELU")
-        if _hid_mask(row_scale) is not None:
-            h[:M] *= _hid_mask(row_scale)   # Dropout on GELU(fc1) (FV:404)
-        ck(lib.fvit_gemm_residual(code, h.data_ptr(), hid, W2.data_ptr(), hid, b2.data_ptr(), None if g is None else g.data_ptr(), y.data_ptr(), C_,
-                                  M, C_, hid, st), "fc2")
-    return _lerp_rows(x, y, row_scale)
+    x1 = attn_block_forward(x, *_attn_args(attn), heads, S, eps, attn.get("scale"), operand_dtype, ra)
+    dx1 = mlp_block_backward(x1, dy, *_mlp_args(mlp), mlp_grads, eps, operand_dtype, rm)
+    return attn_block_backward(x, dx1, *_attn_args(attn), heads, S, attn_grads, eps, attn.get("scale"), operand_dtype, ra)
 
 
 def _carrier_permutations(sr0: int, sr1: int, cw: int, device):
@@ -550,21 +523,17 @@ def _hier_forward_parts(x, ct, hat_attn, hat_mlp, attn, mlp, heads, ws, cw, sr, 
     S = ncw + nloc
     dev = x.device
     dew, win = _carrier_permutations(sr0, sr1, cw, dev)
-    mk = masks or {}
-    r_ha, r_hm, r_a, r_m = _rs(mk, "hat_attn", G), _rs(mk, "hat_mlp", G), _rs(mk, "attn", S), _rs(mk, "mlp", S)
+    r_ha, r_hm, r_a, r_m = _rs(masks, "hat_attn", G), _rs(masks, "hat_mlp", G), _rs(masks, "attn", S), _rs(masks, "mlp", S)
     x0 = (x + pe_x.to(dev)) if pe_x is not None else x
     ct0 = ct[:, dew]
     if pe_ct is not None:
         ct0 = ct0 + pe_ct.to(dev)
     ct0 = ct0.reshape(B * G, C_).contiguous()
-    ha, hm = hat_attn, hat_mlp
-    ct1 = attn_block_forward(ct0, ha["ln_w"], ha["ln_b"], ha["qkv_w"], ha.get("qkv_b"), ha["proj_w"], ha["proj_b"], ha.get("gamma"), ha.get("bias"), heads, G, eps,
-                             ha.get("scale"), od, r_ha)
-    ct2 = mlp_block_forward(ct1, hm["ln_w"], hm["ln_b"], hm["fc1_w"], hm["fc1_b"], hm["fc2_w"], hm["fc2_b"], hm.get("gamma"), eps, od, r_hm)
+    ct1 = attn_block_forward(ct0, *_attn_args(hat_attn), heads, G, eps, hat_attn.get("scale"), od, r_ha)
+    ct2 = mlp_block_forward(ct1, *_mlp_args(hat_mlp), eps, od, r_hm)
     ctw = ct2.view(B, G, C_)[:, win].reshape(Bw, ncw, C_)
     xin = torch.cat((ctw, x0), dim=1).reshape(Bw * S, C_).contiguous()
-    y1 = attn_block_forward(xin, attn["ln_w"], attn["ln_b"], attn["qkv_w"], attn.get("qkv_b"), attn["proj_w"], attn["proj_b"], attn.get("gamma"), attn.get("bias"),
-                            heads, S, eps, attn.get("scale"), od, r_a)
+    y1 = attn_block_forward(xin, *_attn_args(attn), heads, S, eps, attn.get("scale"), od, r_a)
     return dict(ct0=ct0, ct1=ct1, xin=xin, y1=y1, dew=dew, win=win, rows=(r_ha, r_hm, r_a, r_m), S=S, ncw=ncw)
 
 
@@ -582,8 +551,7 @@ def hier_block_backward(x: torch.Tensor, ct: torch.Tensor, dx_out: torch.Tensor,
     DropPath factors; ``prop_grad`` (fp32 [C], optional) receives the propagation's share of d gamma1.  Returns (dx, dct).
     The sub-block backwards run on the kernels; the carrier reshuffles, the concatenation / split and the propagation are row gathers / scatters applied
     with torch indexing."""
-    if not x.is_cuda:
-        raise RuntimeError("hier_block_backward runs only on a HIP device (libfvit_hip.so kernels); there is no CPU fallback")
+    _require_hip("hier_block_backward", x)
     Bw, nloc, C_ = x.shape
     B, G, _ = ct.shape
     sr0, sr1 = int(sr[0]), int(sr[1])
@@ -594,12 +562,11 @@ def hier_block_backward(x: torch.Tensor, ct: torch.Tensor, dx_out: torch.Tensor,
     f = _hier_forward_parts(x, ct, hat_attn, hat_mlp, attn, mlp, heads, ws, cw, sr, pe_x, pe_ct, eps, od, masks)
     S, dew, win = f["S"], f["dew"], f["win"]
     r_ha, r_hm, r_a, r_m = f["rows"]
-    ha, hm = hat_attn, hat_mlp
     # ---- backward ----
     dctw_out = dct_out.reshape(Bw, ncw, C_)
     if prop_gamma is not None:
         # x_out[w, t] = x2[w, t] + gamma1 * ctr[w, up[t]], ctr = the window's carrier rows AFTER the MLP: recompute them
-        y2 = mlp_block_forward(f["y1"], mlp["ln_w"], mlp["ln_b"], mlp["fc1_w"], mlp["fc1_b"], mlp["fc2_w"], mlp["fc2_b"], mlp.get("gamma"), eps, od, r_m).view(Bw, S, C_)
+        y2 = mlp_block_forward(f["y1"], *_mlp_args(mlp), eps, od, r_m).view(Bw, S, C_)
         up = _upsample_index(ws, cw, x.device)
         gam = prop_gamma.detach().float().to(x.device) if isinstance(prop_gamma, torch.Tensor) else None
         if prop_grad is not None and gam is not None:
@@ -607,17 +574,15 @@ def hier_block_backward(x: torch.Tensor, ct: torch.Tensor, dx_out: torch.Tensor,
         contrib = dx_out if gam is None else dx_out * gam
         dctw_out = dctw_out.clone().index_add_(1, up, contrib)
     dy2 = torch.cat((dctw_out, dx_out), dim=1).reshape(Bw * S, C_).contiguous()
-    dy1 = mlp_block_backward(f["y1"], dy2, mlp["ln_w"], mlp["ln_b"], mlp["fc1_w"], mlp["fc1_b"], mlp["fc2_w"], mlp["fc2_b"], mlp.get("gamma"), grads["mlp"], eps, od, r_m)
-    dxin = attn_block_backward(f["xin"], dy1, attn["ln_w"], attn["ln_b"], attn["qkv_w"], attn.get("qkv_b"), attn["proj_w"], attn["proj_b"], attn.get("gamma"),
-                               attn.get("bias"), heads, S, grads["attn"], eps, attn.get("scale"), od, r_a).view(Bw, S, C_)
+    dy1 = mlp_block_backward(f["y1"], dy2, *_mlp_args(mlp), grads["mlp"], eps, od, r_m)
+    dxin = attn_block_backward(f["xin"], dy1, *_attn_args(attn), heads, S, grads["attn"], eps, attn.get("scale"), od, r_a).view(Bw, S, C_)
     dx = dxin[:, ncw:].contiguous()
     dctw = dxin[:, :ncw].reshape(B, G, C_)
     dct2 = torch.empty_like(dctw)
     dct2[:, win] = dctw                                   # adjoint of windowed[:, p] = ct2[:, win[p]]
     dct2 = dct2.reshape(B * G, C_).contiguous()
-    dct1 = mlp_block_backward(f["ct1"], dct2, hm["ln_w"], hm["ln_b"], hm["fc1_w"], hm["fc1_b"], hm["fc2_w"], hm["fc2_b"], hm.get("gamma"), grads["hat_mlp"], eps, od, r_hm)
-    dct0 = attn_block_backward(f["ct0"], dct1, ha["ln_w"], ha["ln_b"], ha["qkv_w"], ha.get("qkv_b"), ha["proj_w"], ha["proj_b"], ha.get("gamma"), ha.get("bias"), heads, G,
-                               grads["hat_attn"], eps, ha.get("scale"), od, r_ha).view(B, G, C_)
+    dct1 = mlp_block_backward(f["ct1"], dct2, *_mlp_args(hat_mlp), grads["hat_mlp"], eps, od, r_hm)
+    dct0 = attn_block_backward(f["ct0"], dct1, *_attn_args(hat_attn), heads, G, grads["hat_attn"], eps, hat_attn.get("scale"), od, r_ha).view(B, G, C_)
     dct = torch.empty_like(dct0)
     dct[:, dew] = dct0                                    # adjoint of dewindowed[:, r] = ct[:, dew[r]]
     return dx, dct
@@ -632,8 +597,7 @@ def hier_block_forward(x: torch.Tensor, ct: torch.Tensor, hat_attn: dict, hat_ml
     B, G, _ = ct.shape
     f = _hier_forward_parts(x, ct, hat_attn, hat_mlp, attn, mlp, heads, ws, cw, sr, pe_x, pe_ct, eps, operand_dtype, masks)
     S, ncw = f["S"], f["ncw"]
-    y2 = mlp_block_forward(f["y1"], mlp["ln_w"], mlp["ln_b"], mlp["fc1_w"], mlp["fc1_b"], mlp["fc2_w"], mlp["fc2_b"], mlp.get("gamma"), eps, operand_dtype,
-                           f["rows"][3]).view(Bw, S, C_)
+    y2 = mlp_block_forward(f["y1"], *_mlp_args(mlp), eps, operand_dtype, f["rows"][3]).view(Bw, S, C_)
     xo, cto = y2[:, ncw:].contiguous(), y2[:, :ncw].reshape(B, G, C_).contiguous()
     if prop_gamma is not None:
         up = _upsample_index(ws, cw, x.device)
@@ -670,13 +634,12 @@ def _emit(sink: Optional[dict], param, g: torch.Tensor) -> None:
     sink[param] = g.clone() if param not in sink else sink[param] + g
 
 
-def _module_params(mods):
+def _params(mods, trainable_only: bool):
+    """The distinct parameters of ``mods`` (None entries skipped), in module order."""
     seen, out = set(), []
     for m in mods:
-        if m is None:
-            continue
-        for prm in m.parameters():
-            if prm.requires_grad and id(prm) not in seen:
+        for prm in (m.parameters() if m is not None else ()):
+            if (prm.requires_grad or not trainable_only) and id(prm) not in seen:
                 seen.add(id(prm))
                 out.append(prm)
     return out
@@ -687,13 +650,21 @@ def _table_grads(sink: Optional[dict], outs, gouts, mods) -> None:
     ``torch.autograd.grad`` -- NOT ``torch.autograd.backward``: a nested backward would run the parameters' AccumulateGrad nodes (and with them
     DDP's reducer hooks) from inside the outer backward, once on a partial gradient and again from the outer pass."""
     live = [(o, g) for o, g in zip(outs, gouts) if o is not None and g is not None and o.requires_grad]
-    params = _module_params(mods)
+    params = _params(mods, True)
     if not live or not params:
         return
     gs = torch.autograd.grad([o for o, _ in live], params, [g.to(o.dtype) for o, g in live], allow_unused=True)
     for prm, g in zip(params, gs):
         if g is not None:
             _emit(sink, prm, g)
+
+
+def _emit_sub(sink: Optional[dict], params: dict, gr) -> None:
+    """Hand over the gradients of one sub-block: ``gr`` (AttnGrads / MlpGrads) names its buffers as the parameter dict names the parameters.  The bias
+    table is no parameter: its gradient continues through ``_table_grads``."""
+    for name, g in vars(gr).items():
+        if g is not None and name != "bias":
+            _emit(sink, params[name], g)
 
 
 def drop_path_masks(layer, batch: int, windows_per_image: int, device, generator=None, operand_dtype=torch.float16):
@@ -753,10 +724,29 @@ def drop_path_masks(layer, batch: int, windows_per_image: int, device, generator
     return out
 
 
-def _pad_map(t: torch.Tensor, ws: int):
-    H, W = t.shape[2:]
-    pb, pr = (ws - H % ws) % ws, (ws - W % ws) % ws
-    return (torch.nn.functional.pad(t, (0, pr, 0, pb)) if (pb or pr) else t), H + pb, W + pr
+def _window_geometry(shape, ws: int):
+    """Window tiling of a (B, C, H, W) map, as (pad, partition, reverse, nh, nw):
+      pad        zeros below / right up to a multiple of ``ws``: F.pad of AR:851-853 on the input and, on dy, the adjoint of the output crop (AR:866-867);
+      partition  padded map -> (B nW, ws^2, C) rows in window order (window_partition FV:83-87);
+      reverse    rows -> map (window_reverse FV:90-93; the two are each other's adjoint), cropped to H x W (on a gradient: the adjoint of the zero padding)."""
+    B, C_, H, W = shape
+    Hp, Wp = H + (ws - H % ws) % ws, W + (ws - W % ws) % ws
+    nh, nw = Hp // ws, Wp // ws
+
+    def pad(t):
+        return torch.nn.functional.pad(t, (0, Wp - W, 0, Hp - H)) if (Hp != H or Wp != W) else t
+
+    def partition(t):
+        return t.reshape(B, C_, nh, ws, nw, ws).permute(0, 2, 4, 3, 5, 1).reshape(B * nh * nw, ws * ws, C_).contiguous()
+
+    def reverse(r):
+        return r.view(B, nh, nw, ws, ws, C_).permute(0, 5, 1, 3, 2, 4).reshape(B, C_, Hp, Wp).contiguous()[:, :, :H, :W]
+
+    return pad, partition, reverse, nh, nw
+
+
+def _block_masks(masks, bi: int):
+    return None if masks is None else masks[bi]
 
 
 def _gm(v):
@@ -785,48 +775,60 @@ def _bias_with_grad(attn, S: int):
     return t, CompactBias(t.detach(), int(w), S - w * w)
 
 
-def _local_params(blk, S):
-    bias_t, bias_arg = _bias_with_grad(blk.attn, S)        # dense (heads, S, S) or compact (heads, (2w-1)^2), differentiable w.r.t. cpb_mlp
-    pe_t = _table_with_grad(blk.pos_embed)                 # (S, C)
-    a = dict(ln_w=blk.norm1.weight, ln_b=blk.norm1.bias, qkv_w=blk.attn.qkv.weight, qkv_b=blk.attn.qkv.bias, proj_w=blk.attn.proj.weight,
-             proj_b=blk.attn.proj.bias, gamma=_gm(blk.gamma3), bias=bias_arg, scale=float(blk.attn.scale))
-    m = dict(ln_w=blk.norm2.weight, ln_b=blk.norm2.bias, fc1_w=blk.mlp.fc1.weight, fc1_b=blk.mlp.fc1.bias, fc2_w=blk.mlp.fc2.weight, fc2_b=blk.mlp.fc2.bias,
-             gamma=_gm(blk.gamma4))
-    return a, m, bias_t, pe_t
+def _attn_dict(norm, at, gamma, bias) -> dict:
+    return dict(ln_w=norm.weight, ln_b=norm.bias, qkv_w=at.qkv.weight, qkv_b=at.qkv.bias, proj_w=at.proj.weight, proj_b=at.proj.bias, gamma=_gm(gamma), bias=bias,
+                scale=float(at.scale))
+
+
+def _mlp_dict(norm, ml, gamma) -> dict:
+    return dict(ln_w=norm.weight, ln_b=norm.bias, fc1_w=ml.fc1.weight, fc1_b=ml.fc1.bias, fc2_w=ml.fc2.weight, fc2_b=ml.fc2.bias, gamma=_gm(gamma))
+
+
+def _block_params(blk, S: int, G: Optional[int] = None):
+    """(parameter dicts of the block's sub-blocks, its folded tables WITH their autograd graphs): attn / mlp and bias (dense (heads, S, S) or compact
+    (heads, (2w-1)^2), differentiable w.r.t. cpb_mlp) / pe_x (ws^2, C); with carrier tokens (``G`` per image) also hat_attn / hat_mlp and hat_bias / pe_ct."""
+    bias_t, bias_arg = _bias_with_grad(blk.attn, S)
+    P = dict(attn=_attn_dict(blk.norm1, blk.attn, blk.gamma3, bias_arg), mlp=_mlp_dict(blk.norm2, blk.mlp, blk.gamma4))
+    t = dict(bias=bias_t, pe_x=_table_with_grad(blk.pos_embed))
+    if G is not None:
+        hat_t, hat_arg = _bias_with_grad(blk.hat_attn, G)
+        P.update(hat_attn=_attn_dict(blk.hat_norm1, blk.hat_attn, blk.gamma1, hat_arg), hat_mlp=_mlp_dict(blk.hat_norm2, blk.hat_mlp, blk.gamma2))
+        t.update(hat_bias=hat_t, pe_ct=_table_with_grad(blk.hat_pos_embed) if hasattr(blk, "hat_pos_embed") and blk.square else None)
+    return P, t
+
+
+def _zero_grads(P: dict, t: dict, C_: int, heads: int, S: int, G: Optional[int], dev) -> dict:
+    """Fresh gradient buffers for the sub-blocks of ``_block_params``, under the same keys."""
+    hid = P["mlp"]["fc1_w"].shape[0]
+    ag = lambda key, n, tab: AttnGrads.zeros(C_, heads, n, dev, with_gamma=P[key]["gamma"] is not None, bias_shape=t[tab].shape)   # noqa: E731
+    mg = lambda key: MlpGrads.zeros(C_, hid, dev, with_gamma=P[key]["gamma"] is not None)   # noqa: E731
+    if G is None:
+        return dict(attn=ag("attn", S, "bias"), mlp=mg("mlp"))
+    return dict(hat_attn=ag("hat_attn", G, "hat_bias"), attn=ag("attn", S, "bias"), hat_mlp=mg("hat_mlp"), mlp=mg("mlp"))
 
 
 def _local_stage_run(layer, x: torch.Tensor, operand_dtype, masks=None):
-    """Forward of a carrier-free stage through the unit kernels: (output map, per-block inputs, per-block parameter dicts, geometry)."""
-    B, C_, H, W = x.shape
+    """Forward of a carrier-free stage through the unit kernels: (output map, per-block inputs, per-block ``_block_params``, geometry)."""
+    C_ = x.shape[1]
     blocks = list(layer.blocks)
     if not blocks or any(b.do_sr_hat for b in blocks):
         raise RuntimeError("local stage: the stage must consist of HAT blocks without carrier tokens")
     ws = blocks[0].window_size
-    xp, Hp, Wp = _pad_map(x.float(), ws)                  # F.pad of AR:851-853 (zeros); the output is cropped back (AR:866-867)
     heads, S = blocks[0].attn.num_heads, ws * ws
     if S > 64 and not _long_enabled(layer):
         raise RuntimeError(f"local stage: windows of {S} tokens (the attention-core backward holds at most 64)")
-    nh, nw = Hp // ws, Wp // ws
-
-    def partition(t):   # (B, C, Hp, Wp) -> (B nW S, C) rows in window order (window_partition FV:83-87)
-        return t.reshape(B, C_, nh, ws, nw, ws).permute(0, 2, 4, 3, 5, 1).reshape(B * nh * nw * S, C_).contiguous()
-
-    def reverse(r):     # rows -> (B, C, Hp, Wp) (window_reverse FV:90-93); the two are each other's adjoint
-        return r.view(B, nh, nw, ws, ws, C_).permute(0, 5, 1, 3, 2, 4).reshape(B, C_, Hp, Wp).contiguous()
-
-    rows = partition(xp)
+    pad, partition, reverse, _, _ = _window_geometry(x.shape, ws)
+    rows = partition(pad(x.float())).view(-1, C_)
     ins, ps = [], []
     for bi, blk in enumerate(blocks):
-        a, m, bias_t, pe_t = _local_params(blk, S)
-        mk = masks[bi] if masks is not None else None
-        xin = (rows.view(-1, S, C_) + pe_t.detach().to(rows.dtype)).reshape(-1, C_).contiguous()
+        P, t = _block_params(blk, S)
+        mk = _block_masks(masks, bi)
+        xin = (rows.view(-1, S, C_) + t["pe_x"].detach().to(rows.dtype)).reshape(-1, C_).contiguous()
         ins.append(xin)
-        ps.append((a, m, bias_t, pe_t))
-        x1 = attn_block_forward(xin, a["ln_w"], a["ln_b"], a["qkv_w"], a["qkv_b"], a["proj_w"], a["proj_b"], a["gamma"], a["bias"], heads, S, 1e-5,
-                                a["scale"], operand_dtype, _rs(mk, "attn", S))
-        rows = mlp_block_forward(x1, m["ln_w"], m["ln_b"], m["fc1_w"], m["fc1_b"], m["fc2_w"], m["fc2_b"], m["gamma"], 1e-5, operand_dtype,
-                                 _rs(mk, "mlp", S))
-    return reverse(rows)[:, :, :H, :W], ins, ps, (partition, reverse, heads, S, Hp, Wp)
+        ps.append((P, t))
+        x1 = attn_block_forward(xin, *_attn_args(P["attn"]), heads, S, 1e-5, P["attn"]["scale"], operand_dtype, _rs(mk, "attn", S))
+        rows = mlp_block_forward(x1, *_mlp_args(P["mlp"]), 1e-5, operand_dtype, _rs(mk, "mlp", S))
+    return reverse(rows), ins, ps, dict(pad=pad, partition=partition, reverse=reverse, heads=heads, S=S)
 
 
 def local_stage_backward(layer, x: torch.Tensor, dy: torch.Tensor, operand_dtype=torch.float16, sink: Optional[dict] = None, masks=None) -> torch.Tensor:
@@ -841,38 +843,21 @@ def local_stage_backward(layer, x: torch.Tensor, dy: torch.Tensor, operand_dtype
 
     Forward activations are recomputed block by block with the unit kernels (one fp32 row checkpoint per block boundary); the block backwards are
     ``local_block_backward``.  The downsample conv of the layer is not part of this path."""
-    if not x.is_cuda:
-        raise RuntimeError("local_stage_backward runs only on a HIP device (libfvit_hip.so kernels); there is no CPU fallback")
-    B, C_, H, W = x.shape
+    _require_hip("local_stage_backward", x)
+    C_ = x.shape[1]
     blocks = list(layer.blocks)
-    _, ins, ps, (partition, reverse, heads, S, Hp, Wp) = _local_stage_run(layer, x, operand_dtype, masks)
-    dyp = torch.nn.functional.pad(dy.float(), (0, Wp - W, 0, Hp - H)) if (Hp != H or Wp != W) else dy.float()   # adjoint of the crop
-    d = partition(dyp)
+    _, ins, ps, gm = _local_stage_run(layer, x, operand_dtype, masks)
+    heads, S = gm["heads"], gm["S"]
+    d = gm["partition"](gm["pad"](dy.float())).view(-1, C_)
     for bi in range(len(blocks) - 1, -1, -1):
-        blk, xin, (a, m, bias_t, pe_t) = blocks[bi], ins[bi], ps[bi]
-        ag = AttnGrads.zeros(C_, heads, S, x.device, with_gamma=a["gamma"] is not None, bias_shape=bias_t.shape)
-        mg = MlpGrads.zeros(C_, m["fc1_w"].shape[0], x.device, with_gamma=m["gamma"] is not None)
-        d = local_block_backward(xin, d, a, m, heads, S, ag, mg, 1e-5, operand_dtype, masks[bi] if masks is not None else None)
-        for prm, g in ((blk.norm1.weight, ag.ln_w), (blk.norm1.bias, ag.ln_b), (blk.attn.qkv.weight, ag.qkv_w), (blk.attn.qkv.bias, ag.qkv_b),
-                       (blk.attn.proj.weight, ag.proj_w), (blk.attn.proj.bias, ag.proj_b), (blk.gamma3, ag.gamma), (blk.norm2.weight, mg.ln_w),
-                       (blk.norm2.bias, mg.ln_b), (blk.mlp.fc1.weight, mg.fc1_w), (blk.mlp.fc1.bias, mg.fc1_b), (blk.mlp.fc2.weight, mg.fc2_w),
-                       (blk.mlp.fc2.bias, mg.fc2_b), (blk.gamma4, mg.gamma)):
-            if g is not None:
-                _emit(sink, prm, g)
+        blk, xin, (P, t) = blocks[bi], ins[bi], ps[bi]
+        grads = _zero_grads(P, t, C_, heads, S, None, x.device)
+        d = local_block_backward(xin, d, P["attn"], P["mlp"], heads, S, grads["attn"], grads["mlp"], 1e-5, operand_dtype, _block_masks(masks, bi))
+        for key, gr in grads.items():
+            _emit_sub(sink, P[key], gr)
         # the folded tables are functions of small MLPs: their gradients continue on the host through the modules' own table() code
-        _table_grads(sink, [bias_t, pe_t], [ag.bias, d.view(-1, S, C_).sum(0)], [blk.attn.pos_emb_funct, blk.pos_embed])
-    return reverse(d)[:, :, :H, :W].contiguous()   # adjoint of the zero padding
-
-
-def _hier_params(blk, S, G):
-    (bias_t, bias_arg), (hat_t, hat_arg) = _bias_with_grad(blk.attn, S), _bias_with_grad(blk.hat_attn, G)
-    t = dict(bias=bias_t, hat_bias=hat_t, pe_x=_table_with_grad(blk.pos_embed),
-             pe_ct=_table_with_grad(blk.hat_pos_embed) if hasattr(blk, "hat_pos_embed") and blk.square else None)
-    mk_a = lambda n, at, g, bias: dict(ln_w=n.weight, ln_b=n.bias, qkv_w=at.qkv.weight, qkv_b=at.qkv.bias, proj_w=at.proj.weight, proj_b=at.proj.bias,   # noqa: E731
-                                       gamma=_gm(g), bias=bias, scale=float(at.scale))
-    mk_m = lambda n, ml, g: dict(ln_w=n.weight, ln_b=n.bias, fc1_w=ml.fc1.weight, fc1_b=ml.fc1.bias, fc2_w=ml.fc2.weight, fc2_b=ml.fc2.bias, gamma=_gm(g))   # noqa: E731
-    return dict(hat_attn=mk_a(blk.hat_norm1, blk.hat_attn, blk.gamma1, hat_arg), hat_mlp=mk_m(blk.hat_norm2, blk.hat_mlp, blk.gamma2),
-                attn=mk_a(blk.norm1, blk.attn, blk.gamma3, bias_arg), mlp=mk_m(blk.norm2, blk.mlp, blk.gamma4)), t
+        _table_grads(sink, [t["bias"], t["pe_x"]], [grads["attn"].bias, d.view(-1, S, C_).sum(0)], [blk.attn.pos_emb_funct, blk.pos_embed])
+    return gm["reverse"](d).contiguous()
 
 
 def _prop_gamma(blk):
@@ -883,41 +868,33 @@ def _prop_gamma(blk):
 
 
 def _hier_stage_run(layer, x: torch.Tensor, operand_dtype, masks=None):
-    B, C_, H, W = x.shape
+    """Forward of a carrier-token stage through the unit kernels: (output map, per-block (rows, ct) checkpoints, per-block ``_block_params``, geometry)."""
+    H, W = x.shape[2:]
     blocks = list(layer.blocks)
     if not blocks or not all(b.do_sr_hat for b in blocks):
         raise RuntimeError("hier stage: the stage must consist of carrier-token HAT blocks")
     b0 = blocks[0]
     ws, cw, sr = b0.window_size, b0.cr_window, tuple(b0.sr_ratio)
+    pad, partition, reverse, nh, nw = _window_geometry(x.shape, ws)
     x_leaf = x.detach().float().requires_grad_(True)
     with torch.enable_grad():
-        xp_leaf, Hp, Wp = _pad_map(x_leaf, ws)           # the TokenInitializer sees the padded map (AR:851-858)
-        if (Hp // ws, Wp // ws) != sr:
-            raise RuntimeError(f"hier stage: map {H}x{W} (padded {Hp}x{Wp}) does not tile into the stage's {sr[0]}x{sr[1]} windows of {ws}")
+        xp_leaf = pad(x_leaf)                            # the TokenInitializer sees the padded map (AR:851-858)
+        if (nh, nw) != sr:
+            raise RuntimeError(f"hier stage: map {H}x{W} (padded {nh * ws}x{nw * ws}) does not tile into the stage's {sr[0]}x{sr[1]} windows of {ws}")
         ct_init = layer.global_tokenizer(xp_leaf)
-    heads, nloc, ncw = b0.attn.num_heads, ws * ws, cw * cw
-    nh, nw = sr
-    G, S = ncw * nh * nw, ncw + nloc
+    heads, ncw = b0.attn.num_heads, cw * cw
+    G, S = ncw * nh * nw, ncw + ws * ws
     if (S > 64 or G > 64) and not _long_enabled(layer):
         raise RuntimeError(f"hier stage: {S} tokens per window / {G} carrier tokens per image (the attention-core backward holds at most 64)")
-
-    def partition(t):
-        return t.reshape(B, C_, nh, ws, nw, ws).permute(0, 2, 4, 3, 5, 1).reshape(B * nh * nw, nloc, C_).contiguous()
-
-    def reverse(r):
-        return r.view(B, nh, nw, ws, ws, C_).permute(0, 5, 1, 3, 2, 4).reshape(B, C_, Hp, Wp).contiguous()
-
     rows, ct = partition(xp_leaf.detach()), ct_init.detach().float().contiguous()
     ckpt, ps = [], []
     for bi, blk in enumerate(blocks):
-        P, t = _hier_params(blk, S, G)
+        P, t = _block_params(blk, S, G)
         ckpt.append((rows, ct))
         ps.append((P, t))
         rows, ct = hier_block_forward(rows, ct, P["hat_attn"], P["hat_mlp"], P["attn"], P["mlp"], heads, ws, cw, sr, t["pe_x"].detach(),
-                                      None if t["pe_ct"] is None else t["pe_ct"].detach(), 1e-5, operand_dtype,
-                                      masks[bi] if masks is not None else None, _prop_gamma(blk))
-    return reverse(rows)[:, :, :H, :W], ckpt, ps, dict(partition=partition, reverse=reverse, heads=heads, S=S, G=G, ws=ws, cw=cw, sr=sr, Hp=Hp, Wp=Wp,
-                                                          x_leaf=x_leaf, ct_init=ct_init)
+                                      None if t["pe_ct"] is None else t["pe_ct"].detach(), 1e-5, operand_dtype, _block_masks(masks, bi), _prop_gamma(blk))
+    return reverse(rows), ckpt, ps, dict(pad=pad, partition=partition, reverse=reverse, heads=heads, S=S, G=G, ws=ws, cw=cw, sr=sr, x_leaf=x_leaf, ct_init=ct_init)
 
 
 def hier_stage_backward(layer, x: torch.Tensor, dy: torch.Tensor, operand_dtype=torch.float16, sink: Optional[dict] = None, masks=None) -> torch.Tensor:
@@ -926,41 +903,25 @@ def hier_stage_backward(layer, x: torch.Tensor, dy: torch.Tensor, operand_dtype=
     returns dx (B, C, H, W) and hands over the gradient of every parameter of ``layer.blocks`` and ``layer.global_tokenizer`` (``.grad`` / ``sink`` as in
     ``local_stage_backward``).  The HAT blocks run on the kernels (``hier_block_forward`` checkpoints per block, ``hier_block_backward``); the TokenInitializer
     (one depthwise conv + average pool, FV:704-738) and the four folded tables per block are small torch modules differentiated by autograd on the host side."""
-    if not x.is_cuda:
-        raise RuntimeError("hier_stage_backward runs only on a HIP device (libfvit_hip.so kernels); there is no CPU fallback")
-    B, C_, H, W = x.shape
+    _require_hip("hier_stage_backward", x)
+    B, C_ = x.shape[:2]
     blocks = list(layer.blocks)
     _, ckpt, ps, gm = _hier_stage_run(layer, x, operand_dtype, masks)
-    heads, S, G, ws, cw, sr, Hp, Wp = gm["heads"], gm["S"], gm["G"], gm["ws"], gm["cw"], gm["sr"], gm["Hp"], gm["Wp"]
-    dyp = torch.nn.functional.pad(dy.float(), (0, Wp - W, 0, Hp - H)) if (Hp != H or Wp != W) else dy.float()
-    d, dct = gm["partition"](dyp), torch.zeros(B, G, C_, dtype=torch.float32, device=x.device)   # the stage's final carrier tokens are dropped (FV:841)
+    heads, S, G, ws, cw, sr = gm["heads"], gm["S"], gm["G"], gm["ws"], gm["cw"], gm["sr"]
+    d = gm["partition"](gm["pad"](dy.float()))
+    dct = torch.zeros(B, G, C_, dtype=torch.float32, device=x.device)   # the stage's final carrier tokens are dropped (FV:841)
     dew, _ = _carrier_permutations(sr[0], sr[1], cw, x.device)
     for bi in range(len(blocks) - 1, -1, -1):
         blk, (xb, ctb), (P, t) = blocks[bi], ckpt[bi], ps[bi]
-        hid = P["mlp"]["fc1_w"].shape[0]
-        grads = dict(hat_attn=AttnGrads.zeros(C_, heads, G, x.device, with_gamma=P["hat_attn"]["gamma"] is not None, bias_shape=t["hat_bias"].shape),
-                     hat_mlp=MlpGrads.zeros(C_, hid, x.device, with_gamma=P["hat_mlp"]["gamma"] is not None),
-                     attn=AttnGrads.zeros(C_, heads, S, x.device, with_gamma=P["attn"]["gamma"] is not None, bias_shape=t["bias"].shape),
-                     mlp=MlpGrads.zeros(C_, hid, x.device, with_gamma=P["mlp"]["gamma"] is not None))
+        grads = _zero_grads(P, t, C_, heads, S, G, x.device)
         pg = _prop_gamma(blk)
         prop_grad = torch.zeros(C_, dtype=torch.float32, device=x.device) if isinstance(pg, torch.Tensor) else None
         d, dct = hier_block_backward(xb, ctb, d, dct, P["hat_attn"], P["hat_mlp"], P["attn"], P["mlp"], heads, ws, cw, sr, t["pe_x"].detach(),
-                                     None if t["pe_ct"] is None else t["pe_ct"].detach(), grads, 1e-5, operand_dtype,
-                                     masks[bi] if masks is not None else None, pg, prop_grad)
+                                     None if t["pe_ct"] is None else t["pe_ct"].detach(), grads, 1e-5, operand_dtype, _block_masks(masks, bi), pg, prop_grad)
         if prop_grad is not None:
             _emit(sink, blk.gamma1, prop_grad)
-        for key, norm, at in (("hat_attn", blk.hat_norm1, blk.hat_attn), ("attn", blk.norm1, blk.attn)):
-            gr = grads[key]
-            for prm, g in ((norm.weight, gr.ln_w), (norm.bias, gr.ln_b), (at.qkv.weight, gr.qkv_w), (at.qkv.bias, gr.qkv_b), (at.proj.weight, gr.proj_w),
-                           (at.proj.bias, gr.proj_b), (blk.gamma1 if key == "hat_attn" else blk.gamma3, gr.gamma)):
-                if g is not None:
-                    _emit(sink, prm, g)
-        for key, norm, ml in (("hat_mlp", blk.hat_norm2, blk.hat_mlp), ("mlp", blk.norm2, blk.mlp)):
-            gr = grads[key]
-            for prm, g in ((norm.weight, gr.ln_w), (norm.bias, gr.ln_b), (ml.fc1.weight, gr.fc1_w), (ml.fc1.bias, gr.fc1_b), (ml.fc2.weight, gr.fc2_w),
-                           (ml.fc2.bias, gr.fc2_b), (blk.gamma2 if key == "hat_mlp" else blk.gamma4, gr.gamma)):
-                if g is not None:
-                    _emit(sink, prm, g)
+        for key, gr in grads.items():
+            _emit_sub(sink, P[key], gr)
         # folded tables -> their small MLPs (host autograd): d pe_x = sum over windows of dx, d pe_ct = sum over images of the dewindowed carrier gradient
         outs, gouts = [t["bias"], t["hat_bias"], t["pe_x"]], [grads["attn"].bias, grads["hat_attn"].bias, d.sum(0)]
         if t["pe_ct"] is not None:
@@ -969,13 +930,13 @@ def hier_stage_backward(layer, x: torch.Tensor, dy: torch.Tensor, operand_dtype=
         _table_grads(sink, outs, gouts, [blk.attn.pos_emb_funct, blk.hat_attn.pos_emb_funct, blk.pos_embed, getattr(blk, "hat_pos_embed", None)])
     # ---- the carrier tokens came from the tokenizer: its conv parameters and its share of dx (autograd.grad: no .grad is touched) ----
     x_leaf, ct_init = gm["x_leaf"], gm["ct_init"]
-    tok_params = _module_params([layer.global_tokenizer])
+    tok_params = _params([layer.global_tokenizer], True)
     gs = torch.autograd.grad([ct_init], tok_params + [x_leaf], [dct.to(ct_init.dtype)], allow_unused=True)
     for prm, g in zip(tok_params, gs[:-1]):
         if g is not None:
             _emit(sink, prm, g)
     dx_tok = gs[-1]
-    dx = gm["reverse"](d)[:, :, :H, :W]
+    dx = gm["reverse"](d)
     return (dx + dx_tok if dx_tok is not None else dx).contiguous()
 
 
@@ -989,15 +950,6 @@ def stage_forward_train(layer, x: torch.Tensor, operand_dtype=torch.float16, mas
 # --------------------------------------------------------------------------------------------------------------------------------------
 # autograd bridge: the transformer branch of a FasterViTLayer as ONE autograd node (forward: fvit_hat_stage_forward, backward: the functions above)
 # --------------------------------------------------------------------------------------------------------------------------------------
-def _stage_params(layer):
-    seen, out = set(), []
-    mods = [layer.blocks] + ([layer.global_tokenizer] if getattr(layer, "do_gt", False) and hasattr(layer, "global_tokenizer") else [])
-    for m in mods:
-        for prm in m.parameters():
-            if id(prm) not in seen:
-                seen.add(id(prm))
-                out.append(prm)
-    return out
 
 
 def operand_torch_dtype(layer) -> torch.dtype:
@@ -1112,4 +1064,5 @@ def stage_forward_with_grad(layer, x: torch.Tensor, operand_dtype=None) -> torch
                            "mode under torch.no_grad() (model.enable_hat_backward(False)).")
     if operand_dtype is None:
         operand_dtype = operand_torch_dtype(layer)
-    return HatStageFunction.apply(x, layer, operand_dtype, *_stage_params(layer))
+    stage_mods = [layer.blocks] + ([layer.global_tokenizer] if getattr(layer, "do_gt", False) and hasattr(layer, "global_tokenizer") else [])
+    return HatStageFunction.apply(x, layer, operand_dtype, *_params(stage_mods, False))
