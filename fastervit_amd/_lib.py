@@ -27,7 +27,7 @@ FVIT_PROF_KINDS = 11
 # every symbol include/fvit_hip.h declares (checked by tests/test_abi.py without a GPU)
 EXPORTED_SYMBOLS = (
     "fvit_abi_version", "fvit_last_error", "fvit_attention_spad", "fvit_attention_dense", "fvit_stage_workspace_bytes", "fvit_workspace_init",
-    "fvit_hat_stage_forward", "fvit_hat_block_forward", "fvit_token_init", "fvit_token_init_dyn", "fvit_feature_tap", "fvit_window_partition", "fvit_window_reverse", "fvit_gemm_bias_act",
+    "fvit_hat_stage_forward", "fvit_hat_block_forward", "fvit_token_init", "fvit_token_init_dyn", "fvit_feature_tap", "fvit_token_init_dyn_backward", "fvit_feature_tap_backward", "fvit_window_partition", "fvit_window_reverse", "fvit_gemm_bias_act",
     "fvit_gemm_residual", "fvit_gemm_terms", "fvit_gemm_residual_splitk", "fvit_gemm_terms_lo", "fvit_window_attention_terms", "fvit_window_attention_long_terms",
     "fvit_gather_layernorm_terms", "fvit_win_mlp_fused_terms", "fvit_win_mlp_split_bytes", "fvit_win_mlp_fused_split", "fvit_win_block_fused_split",
     "fvit_win_block_fused_terms", "fvit_attn_block_fused_terms", "fvit_ct_block_fused_terms", "fvit_window_attention", "fvit_window_attention_long",
@@ -132,6 +132,10 @@ def _declare(lib):
     lib.fvit_token_init_dyn.argtypes = [C.POINTER(FvitMapView), vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]
     lib.fvit_feature_tap.restype = C.c_int
     lib.fvit_feature_tap.argtypes = [C.POINTER(FvitMapView), i32, i32, i32, i32, vp, vp, vp, vp]
+    lib.fvit_token_init_dyn_backward.restype = C.c_int
+    lib.fvit_token_init_dyn_backward.argtypes = [C.POINTER(FvitMapView), vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]
+    lib.fvit_feature_tap_backward.restype = C.c_int
+    lib.fvit_feature_tap_backward.argtypes = [vp, C.POINTER(FvitMapView), C.POINTER(FvitMapView), i32, i32, i32, i32, i32, i32, vp, vp, C.c_int64, vp, vp]
     lib.fvit_window_partition.restype = C.c_int
     lib.fvit_window_partition.argtypes = [C.POINTER(FvitMapView), i32, i32, i32, i32, i32, vp, vp]
     lib.fvit_window_reverse.restype = C.c_int

@@ -784,17 +784,65 @@ def _mlp_dict(norm, ml, gamma) -> dict:
     return dict(ln_w=norm.weight, ln_b=norm.bias, fc1_w=ml.fc1.weight, fc1_b=ml.fc1.bias, fc2_w=ml.fc2.weight, fc2_b=ml.fc2.bias, gamma=_gm(gamma))
 
 
-def _block_params(blk, S: int, G: Optional[int] = None):
+def _grid_table_with_grad(pe, h: int, w: int):
+    """``hat_runtime.grid_pos_table`` (the detection backbone's position table over an h x w grid, normalised by (h * w) // 2) run WITH autograd, so
+    that its gradient continues into the module's cpb_mlp."""
+    from . import hat_runtime
+    fn = getattr(hat_runtime.grid_pos_table, "__wrapped__", hat_runtime.grid_pos_table)
+    with torch.enable_grad():
+        return fn(pe, h, w)
+
+
+def _block_params(blk, S: int, G: Optional[int] = None, grid=None):
     """(parameter dicts of the block's sub-blocks, its folded tables WITH their autograd graphs): attn / mlp and bias (dense (heads, S, S) or compact
-    (heads, (2w-1)^2), differentiable w.r.t. cpb_mlp) / pe_x (ws^2, C); with carrier tokens (``G`` per image) also hat_attn / hat_mlp and hat_bias / pe_ct."""
+    (heads, (2w-1)^2), differentiable w.r.t. cpb_mlp) / pe_x (ws^2, C); with carrier tokens (``G`` per image) also hat_attn / hat_mlp and hat_bias / pe_ct.
+    ``grid`` = (hg, wg), the carrier grid of THIS call of a dynamic-grid layer (the detection backbone; (0, 0) for its carrier-free stages): the position
+    tables follow the detection formulas (``hat_runtime.grid_pos_table``: (ws, ws) for the window, (hg, wg) for the carriers, square or not) and the carrier
+    attention bias, built for the build-time grid, is padded top / left or cropped to G (``PosEmbMLPSwinv2D.table``: F.pad with a negative pad crops)."""
     bias_t, bias_arg = _bias_with_grad(blk.attn, S)
     P = dict(attn=_attn_dict(blk.norm1, blk.attn, blk.gamma3, bias_arg), mlp=_mlp_dict(blk.norm2, blk.mlp, blk.gamma4))
-    t = dict(bias=bias_t, pe_x=_table_with_grad(blk.pos_embed))
+    ws = blk.window_size
+    t = dict(bias=bias_t, pe_x=_table_with_grad(blk.pos_embed) if grid is None else _grid_table_with_grad(blk.pos_embed, ws, ws))
     if G is not None:
         hat_t, hat_arg = _bias_with_grad(blk.hat_attn, G)
         P.update(hat_attn=_attn_dict(blk.hat_norm1, blk.hat_attn, blk.gamma1, hat_arg), hat_mlp=_mlp_dict(blk.hat_norm2, blk.hat_mlp, blk.gamma2))
-        t.update(hat_bias=hat_t, pe_ct=_table_with_grad(blk.hat_pos_embed) if hasattr(blk, "hat_pos_embed") and blk.square else None)
+        if grid is None:
+            pe_ct = _table_with_grad(blk.hat_pos_embed) if hasattr(blk, "hat_pos_embed") and blk.square else None
+        else:
+            pe_ct = _grid_table_with_grad(blk.hat_pos_embed, *grid) if hasattr(blk, "hat_pos_embed") else None
+        t.update(hat_bias=hat_t, pe_ct=pe_ct)
     return P, t
+
+
+def _dynamic(layer) -> bool:
+    """A layer that takes its window grid from the padded input of every call (``BackboneLayer.dynamic_grid``: the detection backbone)."""
+    return bool(getattr(layer, "dynamic_grid", False))
+
+
+TOKEN_INIT_DYN_MAX_PIXELS = 16384   # fvit_token_init_dyn(_backward): one conv-output plane in LDS
+
+
+def token_init_dyn_backward(tok, xp: torch.Tensor, dct: torch.Tensor, ws: int):
+    """Backward of ``hat_runtime.token_init_dyn`` through fvit_token_init_dyn_backward: ``xp`` the (B, C, Hp, Wp) window-padded map of the forward call
+    (any strides; fp32, fp16 or bf16), ``dct`` the fp32 (B, G, C) gradient of the carrier tokens.  Returns (dx fp32 (B, C, Hp, Wp), dweight fp32 (C, 9),
+    dbias fp32 (C,)) -- fresh tensors, nothing is accumulated."""
+    from . import hat_runtime
+    _require_hip("token_init_dyn_backward", xp)
+    B, Cc, Hp, Wp = xp.shape
+    cw = tok.window_size
+    kh, kw, sh, sw, _, _, Hq, Wq = hat_runtime.token_geometry(Hp, Wp, ws, cw)
+    if dct.dtype != torch.float32 or not dct.is_contiguous() or dct.numel() != B * Hq * Wq * Cc or dct.device != xp.device:
+        raise RuntimeError(f"token_init_dyn_backward: dct must be a contiguous fp32 ({B}, {Hq * Wq}, {Cc}) tensor on {xp.device}")
+    with torch.no_grad(), torch.cuda.device(xp.device):
+        w, _ = hat_runtime._token_weights(tok, xp)
+        dx = torch.empty(B, Cc, Hp, Wp, dtype=torch.float32, device=xp.device)
+        dw = torch.empty(Cc, 9, dtype=torch.float32, device=xp.device)
+        db = torch.empty(Cc, dtype=torch.float32, device=xp.device)
+        part = torch.empty(B * Cc * 10, dtype=torch.float32, device=xp.device)
+        rc = _lib.lib().fvit_token_init_dyn_backward(C.byref(hat_runtime._map_view(xp)), w.data_ptr(), dct.data_ptr(), dx.data_ptr(), dw.data_ptr(), db.data_ptr(),
+                                                     part.data_ptr(), B, Cc, Hp, Wp, kh, kw, sh, sw, cw, torch.cuda.current_stream(xp.device).cuda_stream)
+        _lib.check(rc, "fvit_token_init_dyn_backward")
+    return dx, dw, db
 
 
 def _zero_grads(P: dict, t: dict, C_: int, heads: int, S: int, G: Optional[int], dev) -> dict:
@@ -820,8 +868,9 @@ def _local_stage_run(layer, x: torch.Tensor, operand_dtype, masks=None):
     pad, partition, reverse, _, _ = _window_geometry(x.shape, ws)
     rows = partition(pad(x.float())).view(-1, C_)
     ins, ps = [], []
+    grid = (0, 0) if _dynamic(layer) else None
     for bi, blk in enumerate(blocks):
-        P, t = _block_params(blk, S)
+        P, t = _block_params(blk, S, grid=grid)
         mk = _block_masks(masks, bi)
         xin = (rows.view(-1, S, C_) + t["pe_x"].detach().to(rows.dtype)).reshape(-1, C_).contiguous()
         ins.append(xin)
@@ -876,12 +925,25 @@ def _hier_stage_run(layer, x: torch.Tensor, operand_dtype, masks=None):
     b0 = blocks[0]
     ws, cw, sr = b0.window_size, b0.cr_window, tuple(b0.sr_ratio)
     pad, partition, reverse, nh, nw = _window_geometry(x.shape, ws)
-    x_leaf = x.detach().float().requires_grad_(True)
-    with torch.enable_grad():
-        xp_leaf = pad(x_leaf)                            # the TokenInitializer sees the padded map (AR:851-858)
-        if (nh, nw) != sr:
-            raise RuntimeError(f"hier stage: map {H}x{W} (padded {nh * ws}x{nw * ws}) does not tile into the stage's {sr[0]}x{sr[1]} windows of {ws}")
-        ct_init = layer.global_tokenizer(xp_leaf)
+    grid = None
+    if _dynamic(layer):
+        # the detection backbone: the window grid is the one of THIS padded input (b0.sr_ratio is the build-time grid), the carrier grid the tokenizer's
+        # (hg, wg) for it, and the tokenizer runs (and is differentiated, hier_stage_backward) on its own kernels -- no host autograd graph
+        from . import hat_runtime
+        sr = (nh, nw)
+        xp_leaf = pad(x.detach().float())
+        x_leaf = None
+        grid = tuple(hat_runtime.token_geometry(nh * ws, nw * ws, ws, cw)[6:8])
+        if grid != (cw * nh, cw * nw):
+            raise RuntimeError(f"hier stage: carrier grid {grid[0]}x{grid[1]} of a {nh * ws}x{nw * ws} map does not match {nh}x{nw} windows of {cw}x{cw} carriers")
+        ct_init = hat_runtime.token_init_dyn(layer.global_tokenizer, xp_leaf, ws)
+    else:
+        x_leaf = x.detach().float().requires_grad_(True)
+        with torch.enable_grad():
+            xp_leaf = pad(x_leaf)                            # the TokenInitializer sees the padded map (AR:851-858)
+            if (nh, nw) != sr:
+                raise RuntimeError(f"hier stage: map {H}x{W} (padded {nh * ws}x{nw * ws}) does not tile into the stage's {sr[0]}x{sr[1]} windows of {ws}")
+            ct_init = layer.global_tokenizer(xp_leaf)
     heads, ncw = b0.attn.num_heads, cw * cw
     G, S = ncw * nh * nw, ncw + ws * ws
     if (S > 64 or G > 64) and not _long_enabled(layer):
@@ -889,12 +951,13 @@ def _hier_stage_run(layer, x: torch.Tensor, operand_dtype, masks=None):
     rows, ct = partition(xp_leaf.detach()), ct_init.detach().float().contiguous()
     ckpt, ps = [], []
     for bi, blk in enumerate(blocks):
-        P, t = _block_params(blk, S, G)
+        P, t = _block_params(blk, S, G, grid=grid)
         ckpt.append((rows, ct))
         ps.append((P, t))
         rows, ct = hier_block_forward(rows, ct, P["hat_attn"], P["hat_mlp"], P["attn"], P["mlp"], heads, ws, cw, sr, t["pe_x"].detach(),
                                       None if t["pe_ct"] is None else t["pe_ct"].detach(), 1e-5, operand_dtype, _block_masks(masks, bi), _prop_gamma(blk))
-    return reverse(rows), ckpt, ps, dict(pad=pad, partition=partition, reverse=reverse, heads=heads, S=S, G=G, ws=ws, cw=cw, sr=sr, x_leaf=x_leaf, ct_init=ct_init)
+    return reverse(rows), ckpt, ps, dict(pad=pad, partition=partition, reverse=reverse, heads=heads, S=S, G=G, ws=ws, cw=cw, sr=sr, x_leaf=x_leaf, ct_init=ct_init,
+                                         xp=xp_leaf if grid is not None else None)
 
 
 def hier_stage_backward(layer, x: torch.Tensor, dy: torch.Tensor, operand_dtype=torch.float16, sink: Optional[dict] = None, masks=None) -> torch.Tensor:
@@ -928,6 +991,13 @@ def hier_stage_backward(layer, x: torch.Tensor, dy: torch.Tensor, operand_dtype=
             outs.append(t["pe_ct"])
             gouts.append(dct[:, dew].sum(0))
         _table_grads(sink, outs, gouts, [blk.attn.pos_emb_funct, blk.hat_attn.pos_emb_funct, blk.pos_embed, getattr(blk, "hat_pos_embed", None)])
+    if gm["xp"] is not None:
+        # ---- dynamic grid: the tokenizer's backward is fvit_token_init_dyn_backward, on the padded map; the crop is the adjoint of the zero padding ----
+        tok = layer.global_tokenizer
+        dxp, dw, db = token_init_dyn_backward(tok, gm["xp"], dct.contiguous(), ws)
+        _emit(sink, tok.pos_embed.weight, dw)
+        _emit(sink, tok.pos_embed.bias, db)
+        return (gm["reverse"](d) + dxp[:, :, :x.shape[2], :x.shape[3]]).contiguous()
     # ---- the carrier tokens came from the tokenizer: its conv parameters and its share of dx (autograd.grad: no .grad is touched) ----
     x_leaf, ct_init = gm["x_leaf"], gm["ct_init"]
     tok_params = _params([layer.global_tokenizer], True)
@@ -986,15 +1056,23 @@ def backward_unsupported_reason(layer, H: Optional[int] = None, W: Optional[int]
     long = _long_enabled(layer)
     if ws * ws + ncw > 64 and not long:
         return f"windows of {ws * ws + ncw} tokens (the attention-core backward holds at most 64 in LDS)"
+    dyn = _dynamic(layer)
+    if dyn and hier and H is not None:
+        nh_, nw_ = -(-H // ws), -(-W // ws)
+        if nh_ * ws * nw_ * ws > TOKEN_INIT_DYN_MAX_PIXELS:
+            return (f"map {H}x{W} pads to {nh_ * ws}x{nw_ * ws} = {nh_ * ws * nw_ * ws} pixels (the carrier-token initialiser holds one plane of at most "
+                    f"{TOKEN_INIT_DYN_MAX_PIXELS} pixels in LDS)")
     if long and layer.training:
         pd = lambda at: float(getattr(at.attn_drop, "p", 0.0) or 0.0)   # noqa: E731
         G_ = ncw * b0.sr_ratio[0] * b0.sr_ratio[1] if hier else 0
+        if dyn and hier:   # the grid of this call; unknown at enable time (H None): checked at forward time
+            G_ = ncw * (-(-H // ws)) * (-(-W // ws)) if H is not None else 0
         for b in blocks:
             if ws * ws + ncw > 64 and pd(b.attn) > 0:
                 return f"attn_drop = {pd(b.attn)} in train mode on windows of {ws * ws + ncw} tokens (the attention-core backward above 64 tokens has no Dropout mask)"
             if hier and G_ > 64 and pd(b.hat_attn) > 0:
                 return f"attn_drop = {pd(b.hat_attn)} in train mode on {G_} carrier tokens per image (the attention-core backward above 64 tokens has no Dropout mask)"
-    if hier:
+    if hier and not dyn:
         sr = tuple(b0.sr_ratio)
         if ncw * sr[0] * sr[1] > 64 and not long:
             return f"{ncw * sr[0] * sr[1]} carrier tokens per image (at most 64)"
@@ -1026,7 +1104,10 @@ class HatStageFunction(torch.autograd.Function):
             nW = (-(-x.shape[2] // ws)) * (-(-x.shape[3] // ws))
             ctx.masks = drop_path_masks(layer, x.shape[0], nW, x.device, operand_dtype=operand_dtype)
             return stage_forward_train(layer, x.detach(), operand_dtype, ctx.masks)
-        return hat_runtime.stage_forward(layer, x.detach())
+        tok = None
+        if _dynamic(layer) and layer.do_gt and layer.blocks[0].do_sr_hat:   # as BackboneLayer.forward: the tokenizer of this call's geometry
+            tok = lambda xp: hat_runtime.token_init_dyn(layer.global_tokenizer, xp, layer.window_size)  # noqa: E731
+        return hat_runtime.stage_forward(layer, x.detach(), tokenizer=tok)
 
     @staticmethod
     def backward(ctx, dy):
@@ -1066,3 +1147,66 @@ def stage_forward_with_grad(layer, x: torch.Tensor, operand_dtype=None) -> torch
         operand_dtype = operand_torch_dtype(layer)
     stage_mods = [layer.blocks] + ([layer.global_tokenizer] if getattr(layer, "do_gt", False) and hasattr(layer, "global_tokenizer") else [])
     return HatStageFunction.apply(x, layer, operand_dtype, *_params(stage_mods, False))
+
+
+# --------------------------------------------------------------------------------------------------------------------------------------
+# the detection backbone's output tap (crop + eval BatchNorm2d + contiguous NCHW fp32, fvit_feature_tap) as a differentiable op
+# --------------------------------------------------------------------------------------------------------------------------------------
+
+
+def feature_tap_backward(dout: torch.Tensor, x: torch.Tensor, scale: torch.Tensor, H: Optional[int] = None, W: Optional[int] = None):
+    """Backward of ``hat_runtime.feature_tap`` through fvit_feature_tap_backward: ``dout`` fp32 (B, C, H, W), ``x`` the (B, C, Hs, Ws) stage map the forward
+    read (any strides; fp32, fp16 or bf16; H, W default to its extents), ``scale`` fp32 [C] the folded BatchNorm factor.  Returns (dx, sum_d, sum_dx): dx fp32 in
+    x's layout (scale[c] * dout on the crop, zero on the rest of the view) and the per-channel sums of dout and dout * x over the crop."""
+    from . import hat_runtime
+    _require_hip("feature_tap_backward", x)
+    B, Cc, Hs, Ws = x.shape
+    H, W = Hs if H is None else int(H), Ws if W is None else int(W)
+    if tuple(dout.shape) != (B, Cc, H, W) or dout.device != x.device or not (0 < H <= Hs and 0 < W <= Ws):
+        raise RuntimeError(f"feature_tap_backward: dout {tuple(dout.shape)} is not the {H}x{W} crop of the {tuple(x.shape)} map on {x.device}")
+    with torch.no_grad(), torch.cuda.device(x.device):
+        dout = dout.float().contiguous()
+        dx = torch.empty_like(x, dtype=torch.float32)
+        rows = B * Hs * (-(-Ws // 64))
+        part = torch.empty(2 * rows * Cc, dtype=torch.float32, device=x.device)
+        sums = torch.empty(2, Cc, dtype=torch.float32, device=x.device)
+        rc = _lib.lib().fvit_feature_tap_backward(dout.data_ptr(), C.byref(hat_runtime._map_view(x)), C.byref(hat_runtime._map_view(dx)), B, Cc, H, W, Hs, Ws,
+                                                  scale.data_ptr(), part.data_ptr(), part.numel(), sums.data_ptr(),
+                                                  torch.cuda.current_stream(x.device).cuda_stream)
+        _lib.check(rc, "fvit_feature_tap_backward")
+    return dx, sums[0], sums[1]
+
+
+class FeatureTapFunction(torch.autograd.Function):
+    """out = eval BatchNorm2d(x) as contiguous NCHW fp32 (``hat_runtime.feature_tap``) with x and the BatchNorm's weight / bias as differentiable inputs:
+    dx = scale[c] * dout, dbias = sum dout, dweight = (sum dout * x - mean * sum dout) * rsqrt(var + eps), the sums from fvit_feature_tap_backward.  The
+    gradients are RETURNED to autograd (hooks fire once, from the outer engine)."""
+
+    @staticmethod
+    def forward(ctx, x, bn, weight, bias):
+        from . import hat_runtime
+        ctx.bn = bn
+        ctx.save_for_backward(x)
+        return hat_runtime.feature_tap(x.detach(), bn)
+
+    @staticmethod
+    def backward(ctx, dout):
+        from . import hat_runtime
+        (x,) = ctx.saved_tensors
+        bn = ctx.bn
+        scale, _ = hat_runtime._folded_bn(bn, x.device)
+        dx, sd, sdx = feature_tap_backward(dout, x, scale)
+        gw = gb = None
+        if bn.weight is not None and ctx.needs_input_grad[2]:
+            gw = ((sdx.double() - bn.running_mean.double() * sd.double()) * torch.rsqrt(bn.running_var.double() + bn.eps)).to(bn.weight.dtype)
+        if bn.bias is not None and ctx.needs_input_grad[3]:
+            gb = sd.to(bn.bias.dtype)
+        return (dx.to(x.dtype) if ctx.needs_input_grad[0] else None), None, gw, gb
+
+
+def feature_tap_with_grad(x: torch.Tensor, bn) -> torch.Tensor:
+    """``hat_runtime.feature_tap(x, bn)`` as a differentiable op (``bn`` in eval mode: running statistics)."""
+    _require_hip("feature_tap", x)
+    if bn.training:
+        raise RuntimeError("feature_tap_with_grad: the BatchNorm2d is in training mode (batch statistics); the fused tap folds the RUNNING statistics -- run the module")
+    return FeatureTapFunction.apply(x, bn, bn.weight, bn.bias)

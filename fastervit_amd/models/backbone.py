@@ -14,8 +14,21 @@ What differs from the classifier (fastervit_amd/models/faster_vit.py) and where 
   (``hat_runtime.grid_pos_table``); the carrier attention bias is padded (G > 16) or cropped (G < 16) to G (DET:118-135).
 
 Left out on purpose: DET's ``forward_raw`` applies ``permute(0, 3, 1, 2)`` to an NCHW map (a bug: it scrambles the axes); here
-``forward_features`` returns the NCHW maps ``forward`` uses.  The model is inference-only: no backward exists for carrier grids above 64
-tokens, so train mode (with a transformer stage) and gradient requests raise.
+``forward_features`` returns the NCHW maps ``forward`` uses.
+
+Training.  By default the model is inference-only: train mode (with a transformer stage) and gradient requests raise.
+``model.enable_hat_backward()`` opts in to fine-tuning it the way DINO does:
+
+* eval mode with grad enabled: every transformer level is ONE autograd node (forward: the fused inference kernels, backward: the kernel sequence
+  of ``fastervit_amd.hat_backward`` with the window grid, carrier grid, position tables and padded / cropped carrier bias of THAT call, the
+  tokenizer differentiated by ``fvit_token_init_dyn_backward``); the conv levels are PyTorch modules under autograd; every ``norm{i}`` output goes
+  through the differentiable tap (``fvit_feature_tap`` / ``fvit_feature_tap_backward``);
+* train mode: the transformer levels run the unit-kernel chain with stochastic depth and Dropout (masks sized from the padded grid of the call), the
+  conv-side BatchNorms are PyTorch modules, a ``norm{i}`` in training mode runs as ``nn.BatchNorm2d`` on the cropped map (batch statistics), a
+  ``norm{i}`` in eval mode (frozen BN) takes the fused tap;
+* what the kernels do not cover is refused by name at enable time (head_dim > 96, C % 16, hidden % 64, mixed stages) or at forward time (a padded
+  stage map above the tokenizer's 16 384 pixels, ``attn_drop`` in train mode on a window or carrier grid above 64 tokens) -- never from inside
+  ``loss.backward()``.  Parameter gradients are returned to autograd (hooks and DistributedDataParallel see each exactly once).
 """
 from __future__ import annotations
 
@@ -54,7 +67,13 @@ class BackboneLayer(FasterViTLayer):
     dynamic_grid = True   # read by fastervit_amd.hat_runtime
 
     def forward(self, x):
-        if self.transformer_block and len(self.blocks):
+        if self.transformer_block and len(self.blocks) and self.__dict__.get("hat_backward", False) and x.is_cuda and \
+                (self.training or torch.is_grad_enabled()):
+            # FasterViTBackbone.enable_hat_backward: the stage as one autograd node (eval: fused forward; train: unit-kernel chain with stochastic
+            # depth); raises HERE, at forward time, if this call's geometry has no backward
+            from .. import hat_backward
+            x = hat_backward.stage_forward_with_grad(self, x)
+        elif self.transformer_block and len(self.blocks):
             from .. import hat_runtime
             tok = None
             if self.do_gt and self.blocks[0].do_sr_hat:
@@ -144,6 +163,55 @@ class FasterViTBackbone(nn.Module):
                     blk.hat_operand_dtype = name
         return self
 
+    def enable_hat_backward(self, on: bool = True):
+        """Make the backbone differentiable and trainable on the HIP path (off by default: inference-only).  With it on, an eval-mode forward with
+        grad enabled (input and / or parameters requiring grad) and every train-mode forward run the transformer levels through
+        ``fastervit_amd.hat_backward`` (one autograd node per level, per-call geometry) and the ``norm{i}`` outputs through the differentiable
+        feature tap; under ``torch.no_grad()`` in eval mode nothing changes.  Windows and carrier grids of any length are covered (the grids change
+        from call to call, so there is no short-only mode: ``hat_backward_long`` is set on every transformer level).  Refused here, by name:
+        head_dim > 96, C not a multiple of 16, hidden not a multiple of 64, mixed hierarchical / local stages; size-dependent limits are refused at
+        forward time.  ``enable_hat_backward(False)`` restores the inference-only behaviour.  Returns ``self``."""
+        on = bool(on)
+        levels = [lvl for lvl in self.levels if lvl.transformer_block]
+        for lvl in levels:
+            lvl.__dict__["hat_backward_long"] = on
+        if on:
+            from .. import hat_backward
+            for i, lvl in enumerate(self.levels):
+                why = hat_backward.backward_unsupported_reason(lvl) if lvl.transformer_block and len(lvl.blocks) else None
+                if why is not None:
+                    for l2 in levels:
+                        l2.__dict__["hat_backward_long"] = False
+                    raise RuntimeError(f"enable_hat_backward: level {i} of this backbone has no kernel-sequence backward: {why}")
+        self.__dict__["hat_backward"] = on
+        for lvl in levels:
+            lvl.__dict__["hat_backward"] = on
+        return self
+
+    def _wants_grad_path(self, x: torch.Tensor) -> bool:
+        if not self.__dict__.get("hat_backward", False):
+            return False
+        if self.training or any(lvl.training for lvl in self.levels):
+            return True
+        return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
+
+    def _forward_features_grad(self, x: torch.Tensor):
+        """``forward_features`` with autograd (``enable_hat_backward``): see the module docstring."""
+        from ..hat_backward import feature_tap_with_grad
+        from ..hat_runtime import _require_gpu
+        _require_gpu(x, "FasterViTBackbone")
+        x = self.patch_embed(x)
+        outs = []
+        for idx, level in enumerate(self.levels):
+            x, xo = level(x)
+            if idx in self.out_indices:
+                norm = getattr(self, f"norm{idx}")
+                if norm.training:   # batch statistics + running-stat update on the cropped map, as the reference's module call
+                    outs.append(norm(xo).float().contiguous())
+                else:
+                    outs.append(feature_tap_with_grad(xo, norm))
+        return tuple(outs)
+
     def _check_inference(self, x: torch.Tensor) -> None:
         if self.training and any(lvl.transformer_block and len(lvl.blocks) for lvl in self.levels):
             raise RuntimeError("FasterViTBackbone is inference-only: its transformer stages have no backward (carrier grids above 64 tokens); "
@@ -154,6 +222,8 @@ class FasterViTBackbone(nn.Module):
 
     def forward_features(self, x: torch.Tensor):
         """Tuple of the ``out_indices`` levels' normalised pre-downsample maps, NCHW fp32."""
+        if self._wants_grad_path(x):
+            return self._forward_features_grad(x)
         self._check_inference(x)
         from ..hat_runtime import feature_tap
         with torch.no_grad():

@@ -223,6 +223,25 @@ int fvit_token_init_dyn(const FvitMapView* in, const float* weight, const float*
 int fvit_feature_tap(const FvitMapView* in, int32_t batch, int32_t C, int32_t H, int32_t W, const float* scale, const float* shift,
                      float* out, fvit_stream_t stream);
 
+/* Backward of fvit_token_init_dyn (training the detection backbone: fastervit_amd/hat_backward.py).  in / weight / geometry as in the forward call;
+ * dct: f32 (B, G, C) gradient of ct_out, i.e. the contiguous (B, C, Hq, Wq) gradient of the pooled map (its zero-padded rows / columns carry none).
+ * Writes dx f32 (B, C, Hp, Wp) contiguous (the tokenizer's share of the stage input gradient: the caller adds it), dweight f32 [C][9] and dbias f32 [C].
+ * partials: caller-owned scratch of batch * C * 10 floats.  No allocation, no host synchronisation, no atomics: one workgroup per (image, channel)
+ * plane sums in a fixed order and a second launch adds the planes' partials in image order, so a repeated call returns the same bits. */
+int fvit_token_init_dyn_backward(const FvitMapView* in, const float* weight, const float* dct, float* dx, float* dweight, float* dbias,
+                                 float* partials, int32_t batch, int32_t C, int32_t Hp, int32_t Wp, int32_t pool_kh, int32_t pool_kw,
+                                 int32_t pool_sh, int32_t pool_sw, int32_t cw, fvit_stream_t stream);
+
+/* Backward of fvit_feature_tap.  dout: f32 contiguous NCHW (B, C, H, W); x: the stage map the forward read, (B, C, Hs, Ws) with Hs >= H, Ws >= W
+ * through any strides / fp32, fp16, bf16; dx: an f32 view of the same extents (any strides; x's own layout keeps both sides coalesced) that receives
+ * scale[c] * dout on the H x W crop and zero elsewhere.  sums: f32 [2][C] = per-channel sum of dout and of dout * x over the crop, from which the caller
+ * forms the BatchNorm gradients (dbias = sums[0], dweight = (sums[1] - mean * sums[0]) * rsqrt(var + eps)).  partials: caller-owned scratch of
+ * partial_floats >= 2 * B * Hs * ceil(Ws / 64) * C floats.  Two-level sums in a fixed order (64 pixels per wave, then the tile rows per channel): no
+ * atomics, no allocation, no host synchronisation. */
+int fvit_feature_tap_backward(const float* dout, const FvitMapView* x, const FvitMapView* dx, int32_t batch, int32_t C, int32_t H, int32_t W,
+                              int32_t Hs, int32_t Ws, const float* scale, float* partials, int64_t partial_floats, float* sums,
+                              fvit_stream_t stream);
+
 /* window_partition (AR:84-88) / window_reverse (AR:91-94) as standalone ops on f32 token tensors. */
 int fvit_window_partition(const FvitMapView* in, int32_t batch, int32_t C, int32_t Hp, int32_t Wp,
                           int32_t ws, float* windows, fvit_stream_t stream);
