@@ -25,6 +25,9 @@ per-forward path:
     where the consumer is a transformer level; all conv weights are hi + lo; the three Downsample convs and the first stem conv also take their
     input as two terms (hi.hi + hi.lo + lo.hi).  Kernels: ``conv3x3_kernel<.., PX>``, ``ln2d_kernel<.., PX>``, ``stem_conv_kernel<.., PX>``.
 
+Both plans share ONE walk over the levels (``DeployPlan._forward_one``); what differs -- stem, ConvBlocks, the dtype of a transformer level's maps, Downsample,
+head -- sits in the per-step methods behind it, which branch on ``precise``.  The folded weights live in ``plan.t`` as NamedTuples (``ConvWeight``, ``StemW``, ...).
+
 Enabled by ``FasterViT.switch_to_deploy()`` (explicit) or automatically for eval-mode forwards under ``torch.autocast`` with grad
 disabled (``FasterViT.auto_deploy``); module mode (plain nn.Module forward, any dtype) remains the default so that the
 reference's scripts run unchanged.  Logits of the 16-bit plan differ from the fp32 reference by the conv side's 16-bit rounding:
@@ -33,6 +36,7 @@ measured 6.5e-4 .. 9.5e-4 max-abs on FasterViT-0 (asserted < 1e-3 in tests/test_
 from __future__ import annotations
 
 import os
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn.functional as F
@@ -77,6 +81,24 @@ def frag_pack_conv128(w2d: torch.Tensor) -> torch.Tensor:
     return t.permute(0, 3, 1, 4, 2, 5).contiguous().view(4, 36, 2, 64, 8)    # wave, step, ni, (g, s), e
 
 
+class ConvWeight(NamedTuple):
+    """One conv's packed weights (``DeployPlan._cw``)."""
+    wcl: torch.Tensor                    # channels_last 16-bit tensor for F.conv2d (the MIOpen fallback)
+    wk: Optional[torch.Tensor]           # rows of the implicit-GEMM kernel, [Cout][terms][3][3][Cin] or dense-K [Cout][terms][kd]; None: shape not covered
+    wband: Optional[torch.Tensor]        # 128 -> 128 channels: the fragment-order stream of the row-band kernel
+    terms: int                           # weight terms in wk (2 = hi | lo)
+    cv: int                              # channels wk contracts over per tap
+    wk_classic: Optional[torch.Tensor]   # beside a dense-K wk: the classic rows, which the patch form of the kernel takes
+
+
+# the entries of ``DeployPlan.t`` (``_build``); biases and LayerNorm2d parameters are fp32, zero-padded to the map layout
+StemW = NamedTuple("StemW", [("conv0", ConvWeight), ("bias0", torch.Tensor), ("conv1", ConvWeight), ("bias1", torch.Tensor)])     # t["stem"]
+BlockW = NamedTuple("BlockW", [("conv1", ConvWeight), ("bias1", torch.Tensor), ("conv2", ConvWeight), ("bias2", torch.Tensor)])   # t["levels"][i]["blocks"][j]
+DownW = NamedTuple("DownW", [("ln_w", torch.Tensor), ("ln_b", torch.Tensor), ("eps", float), ("conv", ConvWeight), ("cin", int)])  # t["levels"][i]["down"]
+TokW = NamedTuple("TokW", [("w", torch.Tensor), ("bias", torch.Tensor), ("pool_kernel", object), ("pool_stride", object), ("window", int)])  # t["levels"][i]["tok"]: UNUSED (the stage kernels run the tokenizer: fvit_token_init), kept for the layout of t
+HeadW = NamedTuple("HeadW", [("w", torch.Tensor), ("b", torch.Tensor), ("ln", Optional[tuple])])   # t["head"]; ln = (weight, bias, eps) with layer_norm_last
+
+
 class DeployPlan:
     def __init__(self, model, dtype=torch.float16):
         if dtype not in _CODE:
@@ -88,6 +110,11 @@ class DeployPlan:
         self.t = None
         self.zeros = None
         self.streams = 1      # > 1: run the batch as that many shards on separate HIP streams
+        self.shard_sizes = None        # images per shard (a list that sums to the batch); None = equal chunks
+        self.serialize_shards = False  # the shards one after the other on the caller's stream (bench.py's HIP-event pass)
+        self.join_from = None          # level in front of which the shards join (_forward_sharded); None = after the head
+        self.slot_base = 0             # first stage-workspace slot of this plan (_forward_sharded)
+        self._warm_geometries = set()  # shard geometries that have completed one serial pass (_forward_sharded)
         self.side = None
         self.dev = None       # device of the current forward (raw-pointer launches go to torch's current stream on THIS device)
         self.use_hip_conv = True  # fused implicit-GEMM conv kernel where the shape allows; False = MIOpen + glue passes
@@ -136,11 +163,10 @@ class DeployPlan:
         out[:v.numel()] = v
         return out
 
-    def _cw(self, w, terms: int = 1):
-        """(MIOpen weight, HIP-kernel weight, band-kernel weight[, weight terms]): the channels_last 16-bit tensor for F.conv2d, -- when the fused
-        implicit-GEMM kernel supports the shape (3x3, Cin and Cout multiples of 64) -- its [Cout][3][3][Cin] matrix view, and for
-        128 -> 128 channels the fragment-order stream of the row-band kernel.
-        Both channel counts are zero-padded to the map layout (``_cp``)."""
+    def _cw(self, w, terms: int = 1) -> ConvWeight:
+        """``ConvWeight`` of a folded fp32 weight: the channels_last 16-bit tensor for F.conv2d, -- when the fused implicit-GEMM kernel supports
+        the shape (3x3, Cin and Cout multiples of 64) -- its [Cout][3][3][Cin] matrix view, and for 128 -> 128 channels the fragment-order
+        stream of the row-band kernel.  Both channel counts are zero-padded to the map layout (``_cp``)."""
         co0, ci0 = w.shape[:2]
         cop, cip = self._cp(co0), self._cp(ci0)
         if (cop, cip) != (co0, ci0):
@@ -166,39 +192,50 @@ class DeployPlan:
                 # (the classic matrix next to the dense one: the patch form of the kernel -- fvit_conv3x3_patch_form, chosen per call from the map size -- takes it)
                 classic = wk.reshape(co, -1) if lo is None else torch.cat([wk.reshape(co, -1), lo.reshape(co, -1)], dim=1).contiguous()
                 wk = dense(wk) if lo is None else torch.cat([dense(wk), dense(lo)], dim=1).contiguous()
-                return wcl, wk, None, terms, cv, classic
+                return ConvWeight(wcl, wk, None, terms, cv, classic)
             if terms == 2:   # [Cout][hi (3,3,Cin) | lo (3,3,Cin)]: fvit_conv3x3_nhwc_terms
                 wk = torch.cat([wk.reshape(co, -1), lo.reshape(co, -1)], dim=1).contiguous()
-                return wcl, wk, None, 2, cv, None
+                return ConvWeight(wcl, wk, None, 2, cv, None)
             if (co, ci) == (128, 128):   # the fragment-order image fvit_conv3x3_c128_band streams (level 1 of FasterViT-0)
                 wband = frag_pack_conv128(wk.reshape(128, 1152))
-        return wcl, wk, wband, 1, cv, None
+        return ConvWeight(wcl, wk, wband, 1, cv, None)
 
-    def _conv(self, x, w, bias, stride, act, residual=None):
-        """act(conv3x3(x, w) + bias) (+ residual): one fused HIP kernel when supported, else MIOpen conv + glue passes."""
-        wcl, wk, wband, wterms, cv, wk_classic = w
+    # ---- conv launches (both plans) -------------------------------------------------------
+    def _zero_page(self, device):
+        """Pointer to the zero page the conv kernels read for taps outside the image: created lazily, per device (``_hat_prepared`` asks for it)."""
+        if self.zeros is None or self.zeros.device != device:
+            self.zeros = torch.zeros(256, dtype=self.dtype, device=device)
+        return self.zeros.data_ptr()
+
+    @staticmethod
+    def _conv_launch_shape(x, w: ConvWeight, stride):
+        """(weight rows, cv, Co, Ho, Wo) of one implicit-GEMM launch on the map x."""
         B, Ci, Hi, Wi = x.shape
-        if wk is not None and x.is_contiguous(memory_format=torch.channels_last):
-            Co = wk.shape[0]
-            if wk_classic is not None and _lib.lib().fvit_conv3x3_patch_form(B, Hi, Wi, Ci, Co, stride):
-                wk, cv = wk_classic, Ci   # 8 x 16 patches + halo tiles (r06): the classic [Cout][terms][3][3][Cin] rows
-            Ho, Wo = (Hi - 1) // stride + 1, (Wi - 1) // stride + 1
+        wk, cv, Co = w.wk, w.cv, w.wk.shape[0]
+        if w.wk_classic is not None and _lib.lib().fvit_conv3x3_patch_form(B, Hi, Wi, Ci, Co, stride):
+            wk, cv = w.wk_classic, Ci   # 8 x 16 patches + halo tiles (r06): the classic [Cout][terms][3][3][Cin] rows
+        return wk, cv, Co, (Hi - 1) // stride + 1, (Wi - 1) // stride + 1
+
+    def _conv(self, x, w: ConvWeight, bias, stride, act, residual=None):
+        """act(conv3x3(x, w) + bias) (+ residual): one fused HIP kernel when supported, else MIOpen conv + glue passes."""
+        B, Ci, Hi, Wi = x.shape
+        if w.wk is not None and x.is_contiguous(memory_format=torch.channels_last):
+            wk, cv, Co, Ho, Wo = self._conv_launch_shape(x, w, stride)
             out = residual if residual is not None else torch.empty((B, Co, Ho, Wo), dtype=self.dtype, device=x.device,
                                                                     memory_format=torch.channels_last)
-            if self.zeros is None or self.zeros.device != x.device:
-                self.zeros = torch.zeros(256, dtype=self.dtype, device=x.device)
-            if wband is not None and stride == 1 and _lib.lib().fvit_conv3x3_c128_band_supported(Hi, Wi):   # level 1 of FasterViT-0: one row band of an image per workgroup, weights streamed in fragment order
-                rc = _lib.lib().fvit_conv3x3_c128_band(self.code, x.data_ptr(), wband.data_ptr(), bias.data_ptr() if bias is not None else None,
+            zeros = self._zero_page(x.device)
+            if w.wband is not None and stride == 1 and _lib.lib().fvit_conv3x3_c128_band_supported(Hi, Wi):   # level 1 of FasterViT-0: one row band of an image per workgroup, weights streamed in fragment order
+                rc = _lib.lib().fvit_conv3x3_c128_band(self.code, x.data_ptr(), w.wband.data_ptr(), bias.data_ptr() if bias is not None else None,
                                                        residual.data_ptr() if residual is not None else None, out.data_ptr(), B, Hi, Wi, act,
-                                                       self.zeros.data_ptr(), _stream(self.dev))
+                                                       zeros, _stream(self.dev))
                 _lib.check(rc, "fvit_conv3x3_c128_band")
                 return out
             rc = _lib.lib().fvit_conv3x3_nhwc_dense(self.code, x.data_ptr(), wk.data_ptr(), bias.data_ptr() if bias is not None else None,
                                                     residual.data_ptr() if residual is not None else None, out.data_ptr(), B, Hi, Wi,
-                                                    Ci, cv, Co, stride, act, wterms, self.zeros.data_ptr(), _stream(self.dev))
+                                                    Ci, cv, Co, stride, act, w.terms, zeros, _stream(self.dev))
             _lib.check(rc, "fvit_conv3x3_nhwc_dense")
             return out
-        y = F.conv2d(x, wcl, None, stride, 1)
+        y = F.conv2d(x, w.wcl, None, stride, 1)
         if residual is not None:
             return self._bias_residual(residual, y, bias)
         return self._bias_act(y, bias, act) if bias is not None else y
@@ -211,8 +248,8 @@ class DeployPlan:
         w0, b0 = _fold(pe[0], pe[1])
         w1, b1 = _fold(pe[3], pe[4])
         ct = 2 if (self.conv_weight_terms == 2 or self.precise) else 1
-        t["stem"] = (self._cw(w0), self._padv(b0, self._cp(b0.numel())).contiguous(), self._cw(w1, terms=ct),
-                     self._padv(b1, self._cp(b1.numel())).contiguous())
+        t["stem"] = StemW(self._cw(w0), self._padv(b0, self._cp(b0.numel())).contiguous(), self._cw(w1, terms=ct),
+                          self._padv(b1, self._cp(b1.numel())).contiguous())
         t["stem_k"] = t["stem_k_lo"] = None
         # precise plan with a non-standard stem (in_dim != 64 or in_chans != 3): the first conv runs as an fp32 PyTorch-ROCm conv (channels padded)
         co0 = self._cp(w0.shape[0])
@@ -233,18 +270,18 @@ class DeployPlan:
                     wa, ba = _fold(blk.conv1, blk.norm1)
                     wb, bb = _fold(blk.conv2, blk.norm2, blk.gamma if blk.layer_scale else None)
                     cpd = self._cp(ba.numel())
-                    blocks.append((self._cw(wa, terms=ct), self._padv(ba, cpd).contiguous(), self._cw(wb, terms=ct), self._padv(bb, cpd).contiguous()))
+                    blocks.append(BlockW(self._cw(wa, terms=ct), self._padv(ba, cpd).contiguous(), self._cw(wb, terms=ct), self._padv(bb, cpd).contiguous()))
                 e["blocks"] = blocks
             elif getattr(lvl, "do_gt", False):
                 tk = lvl.global_tokenizer
-                e["tok"] = (self._cw(tk.pos_embed.weight.float())[0], tk.pos_embed.bias.to(self.dtype).contiguous(),
-                            tk.to_global_feature.pool.kernel_size, tk.to_global_feature.pool.stride, tk.window_size)
+                e["tok"] = TokW(self._cw(tk.pos_embed.weight.float()).wcl, tk.pos_embed.bias.to(self.dtype).contiguous(),
+                                tk.to_global_feature.pool.kernel_size, tk.to_global_feature.pool.stride, tk.window_size)
             if lvl.downsample is not None:
                 ds = lvl.downsample
                 cin = ds.norm.weight.numel()
-                e["down"] = (self._padv(ds.norm.weight.float(), self._cp(cin)).contiguous(),
-                             self._padv(ds.norm.bias.float(), self._cp(cin)).contiguous(), float(ds.norm.eps),
-                             self._cw(ds.reduction[0].weight.float(), terms=2 if (self.down_weight_terms == 2 or ct == 2) else 1), cin)
+                e["down"] = DownW(self._padv(ds.norm.weight.float(), self._cp(cin)).contiguous(),
+                                  self._padv(ds.norm.bias.float(), self._cp(cin)).contiguous(), float(ds.norm.eps),
+                                  self._cw(ds.reduction[0].weight.float(), terms=2 if (self.down_weight_terms == 2 or ct == 2) else 1), cin)
             t["levels"].append(e)
         if isinstance(m.head, torch.nn.Linear):
             hw = m.head.weight.float()
@@ -254,10 +291,10 @@ class DeployPlan:
             hw, hb = torch.eye(nf, device=m.norm.weight.device), torch.zeros(nf, device=m.norm.weight.device)
         if isinstance(m.norm, torch.nn.BatchNorm2d):
             s, sh = _bn_scale_shift(m.norm)
-            t["head"] = ((hw * s.view(1, -1)).contiguous(), (hb + hw @ sh).contiguous(), None)
+            t["head"] = HeadW((hw * s.view(1, -1)).contiguous(), (hb + hw @ sh).contiguous(), None)
         else:  # layer_norm_last: LayerNorm2d kernel, then pool + head
-            t["head"] = (hw.contiguous(), hb.contiguous(),
-                         (m.norm.weight.float().contiguous(), m.norm.bias.float().contiguous(), float(m.norm.eps)))
+            t["head"] = HeadW(hw.contiguous(), hb.contiguous(),
+                              (m.norm.weight.float().contiguous(), m.norm.bias.float().contiguous(), float(m.norm.eps)))
         self.t = t
 
     # ---- kernels -------------------------------------------------------------------------
@@ -303,16 +340,6 @@ class DeployPlan:
                                                   B * H * W, C, cv, _stream(self.dev)), "fvit_layernorm2d_cl")
         return out
 
-    def _tokenizer(self, tok):
-        w, b, ks, st, cw = tok
-
-        def fn(xp):
-            y = F.avg_pool2d(F.conv2d(xp, w, b, padding=1, groups=xp.shape[1]), ks, st)
-            B, C, H, W = y.shape
-            y = y.reshape(B, C, H // cw, cw, W // cw, cw).permute(0, 2, 4, 3, 5, 1).reshape(B, H * W, C)
-            return y.float().contiguous()
-        return fn
-
     # ---- forward -------------------------------------------------------------------------
     @torch.no_grad()
     def _refresh(self):
@@ -351,15 +378,14 @@ class DeployPlan:
     def _forward_sharded(self, x):
         n = self.streams
         if n <= 1 or x.shape[0] < 2 * n:
-            with hat_runtime.workspace_slot(getattr(self, "slot_base", 0)):
+            with hat_runtime.workspace_slot(self.slot_base):
                 return self._forward_one(x)
         # the batch as n independent shards on n HIP streams (fork / join with events; capturable in a hipGraph): every kernel
         # of this pipeline runs its HBM-bound prologue / epilogue and its MFMA phase in lockstep across workgroups, so two
         # half-size pipelines interleave better than one full-size one
         # slot_base (r06): first workspace slot of this plan; two plans whose forwards are in flight at the same time (inference.PipelinedInference:
         # consecutive steps on alternating streams) must not share the per-(geometry, slot) stage workspaces
-        sb = getattr(self, "slot_base", 0)
-        sizes = getattr(self, "shard_sizes", None)
+        sb, sizes, warm = self.slot_base, self.shard_sizes, self._warm_geometries
         parts = x.split(list(sizes), dim=0) if sizes and sum(sizes) == x.shape[0] and len(sizes) == n else x.chunk(n, dim=0)
         outs = [None] * n
         # weight packing (hat_runtime._prepare) and the zero page are created lazily by the first shard that needs them, on ITS
@@ -369,15 +395,12 @@ class DeployPlan:
         # The per-geometry index tables (an H2D copy) and workspaces are created lazily by the first stage call too: the forked form
         # is allowed only for a (device, shard sizes, image size, operand mode) that has completed one serial pass.
         ops = tuple(getattr(lvl, "hat_operand_dtype", "f16") for lvl in self.model.levels if lvl.transformer_block)
-        wkey = (str(x.device), tuple(p.shape[0] for p in parts), tuple(x.shape[1:]), ops, getattr(self, "join_from", None), sb)
-        warm = self.__dict__.setdefault("_warm_geometries", set())
-        serial = getattr(self, "serialize_shards", False) or not self._hat_prepared(x.device) or wkey not in warm
+        wkey = (str(x.device), tuple(p.shape[0] for p in parts), tuple(x.shape[1:]), ops, self.join_from, sb)
+        serial = self.serialize_shards or not self._hat_prepared(x.device) or wkey not in warm
         # join_from = L (r04, ``plan.join_from``; None = off): the shards run levels [0, L) on their own streams, JOIN, and levels
         # [L, end) + head run once on the whole batch on the caller's stream.  The last stage of FasterViT-0 (one 49-token window per
         # image, 512 channels) is 86-workgroup launches per shard that cannot fill the chip; joined it is 196 / 256 workgroups.
-        jf = getattr(self, "join_from", None)
-        nlev = len(self.model.levels)
-        jf = jf if (jf is not None and 0 < jf < nlev) else None
+        jf = self.join_from if (self.join_from is not None and 0 < self.join_from < len(self.model.levels)) else None
         front = (lambda xi: self._forward_one(xi, 0, jf)) if jf is not None else self._forward_one
         def _cat(xs):   # shards of the precise plan hand on (hi, lo, f32) tuples
             if isinstance(xs[0], tuple):
@@ -414,19 +437,14 @@ class DeployPlan:
         return ShardRunner(self, x, n or max(self.streams, 1))
 
     # ---- the precise plan: two-term / fp32 streams (module docstring) ---------------------------------------------------
-    def _conv_px(self, x, x_lo, w, bias, stride, act, res=None, res_lo=None, want="planes"):
+    def _conv_px(self, x, x_lo, w: ConvWeight, bias, stride, act, res=None, res_lo=None, want="planes"):
         """conv3x3_kernel<.., PX>: x (+ x_lo) -> act(conv + bias) (+ res + res_lo).  ``want``: 'planes' -> (hi, lo) 16-bit planes (in place over the
         residual planes when given), 'single' -> (hi, None), 'f32' -> one fp32 channels_last map."""
-        wcl, wk, wband, wterms, cv, wk_classic = w
-        if wk is None or not x.is_contiguous(memory_format=torch.channels_last):
+        if w.wk is None or not x.is_contiguous(memory_format=torch.channels_last):
             raise RuntimeError("precise deploy plan: this conv shape has no implicit-GEMM kernel (channel counts must pad to multiples of 64)")
         B, Ci, Hi, Wi = x.shape
-        Co = wk.shape[0]
-        if wk_classic is not None and _lib.lib().fvit_conv3x3_patch_form(B, Hi, Wi, Ci, Co, stride):
-            wk, cv = wk_classic, Ci   # the patch form takes the classic rows
-        Ho, Wo = (Hi - 1) // stride + 1, (Wi - 1) // stride + 1
-        if self.zeros is None or self.zeros.device != x.device:
-            self.zeros = torch.zeros(256, dtype=self.dtype, device=x.device)
+        wk, cv, Co, Ho, Wo = self._conv_launch_shape(x, w, stride)
+        zeros = self._zero_page(x.device)
         hi = lo = f32 = None
         if want == "f32":
             f32 = torch.empty((B, Co, Ho, Wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
@@ -438,7 +456,7 @@ class DeployPlan:
                                              bias.data_ptr() if bias is not None else None, res.data_ptr() if res is not None else None,
                                              res_lo.data_ptr() if res_lo is not None else None, hi.data_ptr() if hi is not None else None,
                                              lo.data_ptr() if lo is not None else None, f32.data_ptr() if f32 is not None else None,
-                                             B, Hi, Wi, Ci, cv, Co, stride, act, wterms, self.zeros.data_ptr(), _stream(self.dev))
+                                             B, Hi, Wi, Ci, cv, Co, stride, act, w.terms, zeros, _stream(self.dev))
         _lib.check(rc, "fvit_conv3x3_nhwc_px_dense")
         return f32 if want == "f32" else (hi, lo)
 
@@ -455,144 +473,124 @@ class DeployPlan:
                                                   b.data_ptr(), eps, B * H * W, C, c_valid, _stream(self.dev)), "fvit_layernorm2d_px")
         return hi, lo
 
-    def _forward_one_precise(self, x, lv_from=0, lv_to=None):
-        """``_forward_one`` with every stream as a two-term map ``(hi, lo)`` or an fp32 map.  Between levels the value handed on is the tuple
-        ``(hi, lo, f32)`` (f32 set in front of / behind a transformer level); a partial call (stream shards + join) returns that tuple with the
-        planes concatenated by the caller."""
-        t = self.t
+    # ---- the level walk ----------------------------------------------------------------------------------------------------
+    # The map handed from step to step is one 16-bit channels_last tensor in the 16-bit plan and the tuple ``(hi, lo, f32)`` in the precise plan: two
+    # 16-bit planes (value = hi + lo, f32 = None), or -- in front of / behind a transformer level -- one fp32 map (hi = lo = None).
+    def _forward_one(self, x, lv_from=0, lv_to=None):
+        """Levels [lv_from, lv_to) of the plan; the stem runs in front of level 0, final norm + pool + head after the last level
+        (lv_to = None).  A partial call (stream shards + join) returns the map that the next level takes: the (channels_last, 16-bit) tensor, or
+        the precise plan's ``(hi, lo, f32)``, whose planes the caller concatenates."""
         levels = self.model.levels
         with torch.autocast(device_type="cuda", enabled=False):
             if lv_from == 0:
-                w0, b0, w1, b1 = t["stem"]
-                if t["stem_k"] is None or x.shape[1] != 3 or x.dtype not in hat_runtime._DT:
-                    # a stem other than the reference's 3 -> 64 (in_dim / in_chans kwargs): its first conv as an fp32 PyTorch-ROCm conv
-                    wf, bf, st0 = t["stem0_f32"]
-                    y = torch.relu(F.conv2d(x.float(), wf, bf, st0, 1)).to(self.dtype).contiguous(memory_format=torch.channels_last)
-                else:
-                    B, _, Hi, Wi = x.shape
-                    y = torch.empty((B, 64, (Hi - 1) // 2 + 1, (Wi - 1) // 2 + 1), dtype=self.dtype, device=x.device, memory_format=torch.channels_last)
-                    view = hat_runtime._map_view(x)
-                    _lib.check(_lib.lib().fvit_stem_conv3x3s2_px(self.code, view, t["stem_k"].data_ptr(), t["stem_k_lo"].data_ptr(), b0.data_ptr(),
-                                                                 y.data_ptr(), B, Hi, Wi, _stream(self.dev)), "fvit_stem_conv3x3s2_px")
-                hi, lo = self._conv_px(y, None, w1, b1, 2, 1)
-                f32 = None
-            else:
-                hi, lo, f32 = x
-            for li, (lvl, e) in enumerate(zip(levels, t["levels"])):
+                x = self._stem(x)
+            for li, (lvl, e) in enumerate(zip(levels, self.t["levels"])):
                 if li < lv_from or (lv_to is not None and li >= lv_to):
                     continue
-                if "blocks" in e:
-                    if hi is None:   # a conv level behind a transformer level (no reference entrypoint does this): split the fp32 map
-                        hi = f32.to(self.dtype)
-                        lo = (f32 - hi.float()).to(self.dtype)
-                        f32 = None
-                    for wa, ba, wb, bb in e["blocks"]:
-                        y, _ = self._conv_px(hi, None, wa, ba, 1, 2, want="single")          # conv1 + BN + GELU: an operand, one term
-                        hi, lo = self._conv_px(y, None, wb, bb, 1, 0, res=hi, res_lo=lo)     # conv2 + BN (+ gamma) + residual, in place on the stream
-                else:
-                    if f32 is None:   # a transformer level behind a conv level without a Downsample in between (no reference entrypoint does this)
-                        f32 = hi.float() + lo.float()
-                    creal = lvl.blocks[0].attn.qkv.in_features if len(lvl.blocks) else f32.shape[1]
-                    xin = f32[:, :creal] if f32.shape[1] != creal else f32
-                    cpo = self._cp(creal) if "down" in e else creal
-                    if cpo != creal:
-                        xo = torch.empty((f32.shape[0], cpo, f32.shape[2], f32.shape[3]), dtype=torch.float32, device=f32.device,
-                                         memory_format=torch.channels_last)
-                        xo[:, creal:] = 0
-                        hat_runtime.stage_forward(lvl, xin, out=xo[:, :creal])
-                        f32 = xo
-                    else:
-                        # (an explicit channels_last output: empty_like of the strided channel slice `xin` would be NCHW-contiguous -- uncoalesced
-                        # window_reverse stores and no dense [B][HW][C] image for the pool kernel)
-                        xo = torch.empty((f32.shape[0], creal, f32.shape[2], f32.shape[3]), dtype=torch.float32, device=f32.device,
-                                         memory_format=torch.channels_last)
-                        f32 = hat_runtime.stage_forward(lvl, xin, out=xo)
-                    hi = lo = None
+                x = self._conv_level(x, e["blocks"]) if "blocks" in e else self._hat_level(lvl, x, padded_out="down" in e)
                 if "down" in e:
-                    lw, lb, eps, wd, cin = e["down"]
-                    if f32 is not None and not f32.is_contiguous(memory_format=torch.channels_last):
-                        f32 = f32.contiguous(memory_format=torch.channels_last)
-                    nh, nl = self._ln2d_px(hi, lo, f32, lw, lb, eps, cin)
-                    nxt_transformer = li + 1 < len(levels) and levels[li + 1].transformer_block
-                    if nxt_transformer:
-                        f32 = self._conv_px(nh, nl, wd, None, 2, 0, want="f32")
-                        hi = lo = None
-                    else:
-                        hi, lo = self._conv_px(nh, nl, wd, None, 2, 0)
-                        f32 = None
-            if lv_to is not None:
-                return hi, lo, f32
-            hw, hb, ln = t["head"]
-            if f32 is None:
-                f32 = hi.float() + lo.float()
-            if ln is not None:
-                nh, nl = self._ln2d_px(None, None, f32.contiguous(memory_format=torch.channels_last), *ln, f32.shape[1])
-                f32 = nh.float() + nl.float()
-            return self._pool_head(f32, hw, hb)
+                    x = self._downsample(x, e["down"], f32_out=li + 1 < len(levels) and levels[li + 1].transformer_block)
+            return x if lv_to is not None else self._head(x)
 
-    def _forward_one(self, x, lv_from=0, lv_to=None):
-        """Levels [lv_from, lv_to) of the plan; the stem runs in front of level 0, final norm + pool + head after the last level
-        (lv_to = None).  A partial call returns the (channels_last, 16-bit) map that the next level takes."""
+    def _stem(self, x):
+        """PatchEmbed: conv + BN + ReLU twice, from the caller's image to the map level 0 takes."""
+        t, st = self.t, self.t["stem"]
+        k27 = t["stem_k"] is not None and x.shape[1] == 3 and x.dtype in hat_runtime._DT   # the reference's 3 -> 64 first conv: the K = 27 kernels
         if self.precise:
-            return self._forward_one_precise(x, lv_from, lv_to)
-        t = self.t
-        with torch.autocast(device_type="cuda", enabled=False):
-            w0, b0, w1, b1 = t["stem"]
-            wk1 = w1[1]
-            if lv_from > 0:
-                pass
-            elif (self.fused_stem and t["stem_k"] is not None and x.shape[1] == 3 and x.dtype in hat_runtime._DT and wk1 is not None
-                    and w1[3] == 1 and tuple(wk1.shape) == (64, 3, 3, 64)):
-                B, _, Hi, Wi = x.shape
-                H1, W1 = (Hi - 1) // 2 + 1, (Wi - 1) // 2 + 1
-                y = torch.empty((B, 64, (H1 - 1) // 2 + 1, (W1 - 1) // 2 + 1), dtype=self.dtype, device=x.device,
-                                memory_format=torch.channels_last)
-                view = hat_runtime._map_view(x)
-                _lib.check(_lib.lib().fvit_stem_fused(self.code, view, t["stem_k"].data_ptr(), b0.data_ptr(), wk1.data_ptr(),
-                                                      b1.data_ptr(), y.data_ptr(), B, Hi, Wi, _stream(self.dev)), "fvit_stem_fused")
-                x = y
-            elif t["stem_k"] is not None and x.shape[1] == 3 and x.dtype in hat_runtime._DT:
-                B, _, Hi, Wi = x.shape   # fused stem kernel reads the caller's image in place (any strides, fp32/16-bit)
-                y = torch.empty((B, 64, (Hi - 1) // 2 + 1, (Wi - 1) // 2 + 1), dtype=self.dtype, device=x.device,
-                                memory_format=torch.channels_last)
-                view = hat_runtime._map_view(x)
-                _lib.check(_lib.lib().fvit_stem_conv3x3s2(self.code, view, t["stem_k"].data_ptr(), b0.data_ptr(), y.data_ptr(),
-                                                          B, Hi, Wi, _stream(self.dev)), "fvit_stem_conv3x3s2")
-                x = self._conv(y, w1, b1, 2, 1)
+            if not k27:
+                # a stem other than the reference's 3 -> 64 (in_dim / in_chans kwargs): its first conv as an fp32 PyTorch-ROCm conv
+                wf, bf, st0 = t["stem0_f32"]
+                y = torch.relu(F.conv2d(x.float(), wf, bf, st0, 1)).to(self.dtype).contiguous(memory_format=torch.channels_last)
             else:
-                x = x.to(self.dtype).contiguous(memory_format=torch.channels_last)
-                x = self._conv(self._conv(x, w0, b0, 2, 1), w1, b1, 2, 1)
-            for li, (lvl, e) in enumerate(zip(self.model.levels, t["levels"])):
-                if li < lv_from or (lv_to is not None and li >= lv_to):
-                    continue
-                if "blocks" in e:
-                    for wa, ba, wb, bb in e["blocks"]:
-                        y = self._conv(x, wa, ba, 1, 2)
-                        x = self._conv(y, wb, bb, 1, 0, residual=x)
-                else:
-                    # the HIP stage reads / writes its maps through strided views: the padded map's first C channels in, and
-                    # -- when a Downsample follows -- the first C channels of a zero-initialised padded map out
-                    creal = lvl.blocks[0].attn.qkv.in_features if len(lvl.blocks) else x.shape[1]
-                    xin = x[:, :creal] if x.shape[1] != creal else x
-                    cpo = self._cp(creal) if "down" in e else creal
-                    if cpo != creal:
-                        xo = torch.empty((x.shape[0], cpo, x.shape[2], x.shape[3]), dtype=self.dtype, device=x.device,
-                                         memory_format=torch.channels_last)
-                        xo[:, creal:] = 0   # only the pad channels need initialising; the stage writes the first creal
-                        hat_runtime.stage_forward(lvl, xin, out=xo[:, :creal])  # TokenInitializer: fvit_token_init in both modes
-                        x = xo
-                    else:
-                        xo = torch.empty((x.shape[0], creal, x.shape[2], x.shape[3]), dtype=self.dtype, device=x.device, memory_format=torch.channels_last)
-                        x = hat_runtime.stage_forward(lvl, xin, out=xo)   # (explicit channels_last output: see _forward_one_precise)
-                if "down" in e:
-                    lw, lb, eps, wd, cin = e["down"]
-                    x = self._conv(self._ln2d(x, lw, lb, eps, cin), wd, None, 2, 0)
-            if lv_to is not None:
-                return x
-            hw, hb, ln = t["head"]
-            if ln is not None:
-                x = self._ln2d(x, *ln)
-            return self._pool_head(x, hw, hb)
+                B, _, Hi, Wi = x.shape
+                y = torch.empty((B, 64, (Hi - 1) // 2 + 1, (Wi - 1) // 2 + 1), dtype=self.dtype, device=x.device, memory_format=torch.channels_last)
+                view = hat_runtime._map_view(x)
+                _lib.check(_lib.lib().fvit_stem_conv3x3s2_px(self.code, view, t["stem_k"].data_ptr(), t["stem_k_lo"].data_ptr(), st.bias0.data_ptr(),
+                                                             y.data_ptr(), B, Hi, Wi, _stream(self.dev)), "fvit_stem_conv3x3s2_px")
+            return (*self._conv_px(y, None, st.conv1, st.bias1, 2, 1), None)
+        wk1 = st.conv1.wk
+        if self.fused_stem and k27 and wk1 is not None and st.conv1.terms == 1 and tuple(wk1.shape) == (64, 3, 3, 64):
+            B, _, Hi, Wi = x.shape
+            H1, W1 = (Hi - 1) // 2 + 1, (Wi - 1) // 2 + 1
+            y = torch.empty((B, 64, (H1 - 1) // 2 + 1, (W1 - 1) // 2 + 1), dtype=self.dtype, device=x.device,
+                            memory_format=torch.channels_last)
+            view = hat_runtime._map_view(x)
+            _lib.check(_lib.lib().fvit_stem_fused(self.code, view, t["stem_k"].data_ptr(), st.bias0.data_ptr(), wk1.data_ptr(),
+                                                  st.bias1.data_ptr(), y.data_ptr(), B, Hi, Wi, _stream(self.dev)), "fvit_stem_fused")
+            return y
+        if k27:
+            B, _, Hi, Wi = x.shape   # fused stem kernel reads the caller's image in place (any strides, fp32/16-bit)
+            y = torch.empty((B, 64, (Hi - 1) // 2 + 1, (Wi - 1) // 2 + 1), dtype=self.dtype, device=x.device,
+                            memory_format=torch.channels_last)
+            view = hat_runtime._map_view(x)
+            _lib.check(_lib.lib().fvit_stem_conv3x3s2(self.code, view, t["stem_k"].data_ptr(), st.bias0.data_ptr(), y.data_ptr(),
+                                                      B, Hi, Wi, _stream(self.dev)), "fvit_stem_conv3x3s2")
+            return self._conv(y, st.conv1, st.bias1, 2, 1)
+        x = x.to(self.dtype).contiguous(memory_format=torch.channels_last)
+        return self._conv(self._conv(x, st.conv0, st.bias0, 2, 1), st.conv1, st.bias1, 2, 1)
+
+    def _conv_level(self, x, blocks):
+        """The ConvBlocks of a level, in place on the stream."""
+        if not self.precise:
+            for b in blocks:
+                y = self._conv(x, b.conv1, b.bias1, 1, 2)
+                x = self._conv(y, b.conv2, b.bias2, 1, 0, residual=x)
+            return x
+        hi, lo, f32 = x
+        if hi is None:   # a conv level behind a transformer level (no reference entrypoint does this): split the fp32 map
+            hi = f32.to(self.dtype)
+            lo = (f32 - hi.float()).to(self.dtype)
+        for b in blocks:
+            y, _ = self._conv_px(hi, None, b.conv1, b.bias1, 1, 2, want="single")              # conv1 + BN + GELU: an operand, one term
+            hi, lo = self._conv_px(y, None, b.conv2, b.bias2, 1, 0, res=hi, res_lo=lo)         # conv2 + BN (+ gamma) + residual, in place on the stream
+        return hi, lo, None
+
+    def _hat_level(self, lvl, x, padded_out):
+        """A transformer level (``hat_runtime.stage_forward``) on a 16-bit map, or -- precise plan -- from and to an fp32 map."""
+        if self.precise:
+            hi, lo, x = x
+            if x is None:   # a transformer level behind a conv level without a Downsample in between (no reference entrypoint does this)
+                x = hi.float() + lo.float()
+        # the HIP stage reads / writes its maps through strided views: the padded map's first C channels in, and
+        # -- when a Downsample follows -- the first C channels of a zero-initialised padded map out
+        creal = lvl.blocks[0].attn.qkv.in_features if len(lvl.blocks) else x.shape[1]
+        xin = x[:, :creal] if x.shape[1] != creal else x
+        cpo = self._cp(creal) if padded_out else creal
+        # (an explicit channels_last output: empty_like of the strided channel slice `xin` would be NCHW-contiguous -- uncoalesced
+        # window_reverse stores and no dense [B][HW][C] image for the pool kernel)
+        xo = torch.empty((x.shape[0], cpo, x.shape[2], x.shape[3]), dtype=torch.float32 if self.precise else self.dtype, device=x.device,
+                         memory_format=torch.channels_last)
+        if cpo != creal:
+            xo[:, creal:] = 0   # only the pad channels need initialising; the stage writes the first creal
+            hat_runtime.stage_forward(lvl, xin, out=xo[:, :creal])  # TokenInitializer: fvit_token_init in both modes
+        else:
+            xo = hat_runtime.stage_forward(lvl, xin, out=xo)
+        return (None, None, xo) if self.precise else xo
+
+    def _downsample(self, x, d: DownW, f32_out):
+        """Downsample: LayerNorm2d + strided bias-free conv.  ``f32_out``: a transformer level follows, which the precise plan feeds an fp32 map."""
+        if not self.precise:
+            return self._conv(self._ln2d(x, d.ln_w, d.ln_b, d.eps, d.cin), d.conv, None, 2, 0)
+        hi, lo, f32 = x
+        if f32 is not None and not f32.is_contiguous(memory_format=torch.channels_last):
+            f32 = f32.contiguous(memory_format=torch.channels_last)
+        nh, nl = self._ln2d_px(hi, lo, f32, d.ln_w, d.ln_b, d.eps, d.cin)
+        if f32_out:
+            return None, None, self._conv_px(nh, nl, d.conv, None, 2, 0, want="f32")
+        return (*self._conv_px(nh, nl, d.conv, None, 2, 0), None)
+
+    def _head(self, x):
+        """Final norm + AdaptiveAvgPool2d(1) + head -> fp32 logits."""
+        hw, hb, ln = self.t["head"]
+        if not self.precise:
+            return self._pool_head(x if ln is None else self._ln2d(x, *ln), hw, hb)
+        hi, lo, f32 = x
+        if f32 is None:
+            f32 = hi.float() + lo.float()
+        if ln is not None:
+            nh, nl = self._ln2d_px(None, None, f32.contiguous(memory_format=torch.channels_last), *ln, f32.shape[1])
+            f32 = nh.float() + nl.float()
+        return self._pool_head(f32, hw, hb)
 
 
 class ShardRunner:

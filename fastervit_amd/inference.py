@@ -120,7 +120,7 @@ class PipelinedInference:
     def __init__(self, model, example: torch.Tensor, depth: int = 2, streams: int = 1, first: Optional[CompiledInference] = None, cu_masks=None, **kw):
         self.depth = max(1, int(depth))
         # ``first``: an existing runner of the same configuration (slot base 0) to use as runner 0
-        if first is not None and getattr(first.plan, "slot_base", 0) != 0:
+        if first is not None and first.plan.slot_base != 0:
             raise ValueError("PipelinedInference: the runner passed as `first` must use workspace slot base 0")
         # runner i owns workspace slots [i * stride, (i + 1) * stride): the stride covers the stream shards of every runner, ``first`` included
         # (a ``first`` with more shards than ``streams`` would otherwise share its upper slots -- and their split-kernel counters -- with runner 1)

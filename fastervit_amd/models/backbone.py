@@ -36,7 +36,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .faster_vit import FasterViTLayer, PatchEmbed
+from .faster_vit import FasterViTLayer, HatSwitches, PatchEmbed
 
 # DET:853-960, the builder's eight configurations
 _BACKBONE_CFGS = {
@@ -93,7 +93,7 @@ class BackboneLayer(FasterViTLayer):
         return (x if self.downsample is None else self.downsample(x)), x
 
 
-class FasterViTBackbone(nn.Module):
+class FasterViTBackbone(HatSwitches, nn.Module):
     """DET:710-850.  ``forward(tensor_list)`` takes any object with ``.tensors`` (B, 3, H, W) and ``.mask`` (B, H, W) and returns
     ``{k: type(tensor_list)(feature, mask)}`` for the k-th entry of ``out_indices``; ``forward_features(x)`` returns the tuple of NCHW
     fp32 maps.  Any H, W: detection batches change size from call to call."""
@@ -144,25 +144,6 @@ class FasterViTBackbone(nn.Module):
         self._freeze_stages()
         return self
 
-    def set_hat_operand_dtype(self, name: str):
-        """Operand mode of the HAT kernels, as ``FasterViT.set_hat_operand_dtype``: 'f16' (default), 'bf16', 'f16x2', 'bf16x2', 'f16x3',
-        'bf16x3'."""
-        from ..hat_runtime import OPERAND_MODES, x3_unsupported_reason
-        if name not in OPERAND_MODES:
-            raise ValueError(f"operand mode must be one of {OPERAND_MODES}")
-        if name.endswith("x3"):
-            for li, lvl in enumerate(self.levels):
-                why = x3_unsupported_reason(lvl) if lvl.transformer_block and len(lvl.blocks) else None
-                if why is not None:
-                    raise NotImplementedError(f"operand mode {name!r}, level {li}: {why}")
-        self.hat_operand_dtype = name
-        for lvl in self.levels:
-            lvl.hat_operand_dtype = name
-            if lvl.transformer_block:
-                for blk in lvl.blocks:
-                    blk.hat_operand_dtype = name
-        return self
-
     def enable_hat_backward(self, on: bool = True):
         """Make the backbone differentiable and trainable on the HIP path (off by default: inference-only).  With it on, an eval-mode forward with
         grad enabled (input and / or parameters requiring grad) and every train-mode forward run the transformer levels through
@@ -171,22 +152,8 @@ class FasterViTBackbone(nn.Module):
         from call to call, so there is no short-only mode: ``hat_backward_long`` is set on every transformer level).  Refused here, by name:
         head_dim > 96, C not a multiple of 16, hidden not a multiple of 64, mixed hierarchical / local stages; size-dependent limits are refused at
         forward time.  ``enable_hat_backward(False)`` restores the inference-only behaviour.  Returns ``self``."""
-        on = bool(on)
-        levels = [lvl for lvl in self.levels if lvl.transformer_block]
-        for lvl in levels:
-            lvl.__dict__["hat_backward_long"] = on
-        if on:
-            from .. import hat_backward
-            for i, lvl in enumerate(self.levels):
-                why = hat_backward.backward_unsupported_reason(lvl) if lvl.transformer_block and len(lvl.blocks) else None
-                if why is not None:
-                    for l2 in levels:
-                        l2.__dict__["hat_backward_long"] = False
-                    raise RuntimeError(f"enable_hat_backward: level {i} of this backbone has no kernel-sequence backward: {why}")
-        self.__dict__["hat_backward"] = on
-        for lvl in levels:
-            lvl.__dict__["hat_backward"] = on
-        return self
+        # the grids change from call to call: long sequences always on; a refusal leaves the flag on the levels, False
+        return self._set_hat_backward(bool(on), bool(on), "backbone", refused_long=False)
 
     def _wants_grad_path(self, x: torch.Tensor) -> bool:
         if not self.__dict__.get("hat_backward", False):

@@ -421,7 +421,57 @@ class FasterViTLayer(nn.Module):
         return x if self.downsample is None else self.downsample(x)
 
 
-class FasterViT(nn.Module):
+class HatSwitches:
+    """The model-level switches of the HAT kernels, shared by ``FasterViT`` and ``models.backbone.FasterViTBackbone`` (both hold ``self.levels``)."""
+
+    def set_hat_operand_dtype(self, name: str):
+        """Choose the operand mode of the HAT kernels (fp32 accumulate): 'f16' (default) or 'bf16' -- 16-bit operands rounded once --
+        or 'f16x2' / 'bf16x2' -- every Linear weight as two 16-bit terms hi + lo (twice the MFMA work on the weights' side; the
+        route to logits max-abs < 1e-3 with bf16 operands, DESIGN.md section 2) -- or 'f16x3' / 'bf16x3' -- weights AND activations
+        as two terms (three times the MFMA work, unfused kernel chain): ~22 significant bits through the HAT stages, the route to
+        logits max-abs < 1e-3 ABSOLUTE on FasterViT-4 / any-res (measured 2.6e-5 on |7.1| with the fp32 conv side)."""
+        from ..hat_runtime import OPERAND_MODES, x3_unsupported_reason
+        if name not in OPERAND_MODES:
+            raise ValueError(f"operand mode must be one of {OPERAND_MODES}")
+        if name.endswith("x3"):
+            # geometry the two-term-activation kernels do not cover is refused HERE, by name, not as an error of the first forward (VERDICT r05 item 12)
+            for li, lvl in enumerate(self.levels):
+                why = x3_unsupported_reason(lvl) if lvl.transformer_block and len(lvl.blocks) else None
+                if why is not None:
+                    raise NotImplementedError(f"operand mode {name!r}, level {li}: {why}")
+        self.hat_operand_dtype = name
+        for lvl in self.levels:
+            lvl.hat_operand_dtype = name
+            if lvl.transformer_block:
+                for blk in lvl.blocks:   # the block-level API (HAT.forward -> hat_runtime.block_forward) reads the mode from the block
+                    blk.hat_operand_dtype = name
+        return self
+
+    def _set_hat_backward(self, on: bool, long_on: bool, owner: str, refused_long):
+        """``enable_hat_backward`` of both classes: store ``hat_backward_long`` on every transformer level, validate every stage (``on``), then
+        store ``hat_backward`` on the model and its transformer levels.  A refusal names ``owner`` and leaves ``hat_backward_long`` at
+        ``refused_long`` (None: removed)."""
+        levels = [lvl for lvl in self.levels if lvl.transformer_block]
+        for lvl in levels:
+            lvl.__dict__["hat_backward_long"] = long_on
+        if on:
+            from .. import hat_backward
+            for i, lvl in enumerate(self.levels):
+                why = hat_backward.backward_unsupported_reason(lvl) if lvl.transformer_block and len(lvl.blocks) else None
+                if why is not None:
+                    for l2 in levels:
+                        if refused_long is None:
+                            l2.__dict__.pop("hat_backward_long", None)
+                        else:
+                            l2.__dict__["hat_backward_long"] = refused_long
+                    raise RuntimeError(f"enable_hat_backward: level {i} of this {owner} has no kernel-sequence backward: {why}")
+        self.__dict__["hat_backward"] = on
+        for lvl in levels:
+            lvl.__dict__["hat_backward"] = on
+        return self
+
+
+class FasterViT(HatSwitches, nn.Module):
     """FV:846-972 / AR:873-1002."""
 
     def __init__(self, dim, in_dim, depths, window_size, ct_size, mlp_ratio, num_heads, resolution=224,
@@ -468,29 +518,6 @@ class FasterViT(nn.Module):
     @torch.jit.ignore
     def no_weight_decay_keywords(self):
         return {"rpb"}
-
-    def set_hat_operand_dtype(self, name: str):
-        """Choose the operand mode of the HAT kernels (fp32 accumulate): 'f16' (default) or 'bf16' -- 16-bit operands rounded once --
-        or 'f16x2' / 'bf16x2' -- every Linear weight as two 16-bit terms hi + lo (twice the MFMA work on the weights' side; the
-        route to logits max-abs < 1e-3 with bf16 operands, DESIGN.md section 2) -- or 'f16x3' / 'bf16x3' -- weights AND activations
-        as two terms (three times the MFMA work, unfused kernel chain): ~22 significant bits through the HAT stages, the route to
-        logits max-abs < 1e-3 ABSOLUTE on FasterViT-4 / any-res (measured 2.6e-5 on |7.1| with the fp32 conv side)."""
-        from ..hat_runtime import OPERAND_MODES, x3_unsupported_reason
-        if name not in OPERAND_MODES:
-            raise ValueError(f"operand mode must be one of {OPERAND_MODES}")
-        if name.endswith("x3"):
-            # geometry the two-term-activation kernels do not cover is refused HERE, by name, not as an error of the first forward (VERDICT r05 item 12)
-            for li, lvl in enumerate(self.levels):
-                why = x3_unsupported_reason(lvl) if lvl.transformer_block and len(lvl.blocks) else None
-                if why is not None:
-                    raise NotImplementedError(f"operand mode {name!r}, level {li}: {why}")
-        self.hat_operand_dtype = name
-        for lvl in self.levels:
-            lvl.hat_operand_dtype = name
-            if lvl.transformer_block:
-                for blk in lvl.blocks:   # the block-level API (HAT.forward -> hat_runtime.block_forward) reads the mode from the block
-                    blk.hat_operand_dtype = name
-        return self
 
     def switch_to_deploy(self, dtype=torch.float16, streams=1):
         """Opt-in inference plan for the conv side (fastervit_amd/conv_runtime.py): BatchNorm folded into the conv
@@ -560,7 +587,7 @@ class FasterViT(nn.Module):
         return plans[dt], dt
 
     def compile_inference(self, example: torch.Tensor, dtype=torch.float16, streams: int = 3, graph: bool = True, join_from=None, conv_down_terms=None,
-                          precise: bool = False):
+                          precise=None):
         """Throughput entry point: the deploy plan with ``streams`` stream shards captured ONCE into a hipGraph
         with static input / output buffers; returns a callable ``runner(x) -> logits`` that copies ``x`` in and replays the
         graph (any batch size up to the example's; shorter batches are zero-padded and the result sliced).  See
@@ -570,7 +597,7 @@ class FasterViT(nn.Module):
                                  precise=precise)
 
     def pipelined_inference(self, example: torch.Tensor, depth: int = 2, dtype=torch.float16, streams: int = 1, graph: bool = True, join_from=None,
-                            conv_down_terms=None, precise: bool = False):
+                            conv_down_terms=None, precise=None):
         """Throughput entry point with ``depth`` whole-batch steps in flight (r06; what ``bench.py`` times): ``depth`` runners of ``compile_inference``'s
         configuration, step k replayed on stream k % depth, so the tail of a step (last stage, head) overlaps the stem / conv levels of the next one.
         ``p.launch()`` enqueues one step and returns its runner (logits in ``runner.static_y`` after ``p.wait()``).  See
@@ -589,24 +616,8 @@ class FasterViT(nn.Module):
         576 / 1024 / 2304 tokens), the any-res models on large inputs -- through the tiled MFMA attention backward (fvit_bwd_window_attention_long); the flag
         is stored on every transformer level (``level.hat_backward_long``) and holds in eval AND train mode.  Still refused, by name and at forward time:
         head_dim > 96, and ``attn_drop_rate`` > 0 in train mode on such a sequence.  With the default ``False`` nothing changes."""
-        long_on = bool(on and long_sequences)
-        for lvl in self.levels:
-            if lvl.transformer_block:
-                lvl.__dict__["hat_backward_long"] = long_on
-        if on:
-            from .. import hat_backward
-            for i, lvl in enumerate(self.levels):
-                if lvl.transformer_block and len(lvl.blocks):
-                    why = hat_backward.backward_unsupported_reason(lvl)
-                    if why is not None:
-                        for l2 in self.levels:
-                            l2.__dict__.pop("hat_backward_long", None)
-                        raise RuntimeError(f"enable_hat_backward: level {i} of this model has no kernel-sequence backward: {why}")
-        self.__dict__["hat_backward"] = bool(on)
-        for lvl in self.levels:
-            if lvl.transformer_block:
-                lvl.__dict__["hat_backward"] = bool(on)
-        return self
+        # long sequences are opt-in here; a refusal leaves the levels without the flag, as before any call
+        return self._set_hat_backward(bool(on), bool(on and long_sequences), "model", refused_long=None)
 
     def forward(self, x):
         self._check_grad_request(x)   # eval on the GPU, forward-only HIP stages: a caller asking for d/dx gets the gradient or an error, not zeros

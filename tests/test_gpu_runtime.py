@@ -312,3 +312,30 @@ def test_reference_shaped_eval_loop_on_the_hip_path():
     runner = model.compile_inference(example, streams=2)
     n2, d1, d5, last2 = evaluate(model, loader, torch.device("cuda"), channels_last=True, runner=runner)
     assert (n2, d1, d5) == (rn, r1, r5) and max_abs(last2.float().cpu(), logits_all[-1]) < 1e-3
+
+
+@pytest.mark.parametrize("precise", [False, True], ids=["16bit", "precise-f16x3"])
+@pytest.mark.parametrize("name", ["tiny_hier", "tiny_anyres"])
+def test_partial_level_walks_compose_bitwise(name, precise):
+    """``DeployPlan._forward_one`` is the one walk over the levels of both plans, and a partial call hands on exactly what the next level takes (one
+    16-bit map, or the precise plan's ``(hi, lo, f32)``): for EVERY split point k, levels [0, k) followed by levels [k, end) + head give the bits
+    of the whole walk.  tiny_hier: 24 / 48 / 96 / 192 channels, so the transformer level in front of a Downsample writes a channel-padded map;
+    tiny_anyres: 64 channels there (unpadded output, Downsample behind it), non-square maps.  Stream shards with ``join_from`` use k = 3 only."""
+    from tests.synth import synth_input
+    from tests.cases import SEED
+    model, _ = build_product_model(name, "cuda")
+    if precise:
+        model.set_hat_operand_dtype("f16x3")
+    x = synth_input(4, *CASES[name]["hw"], SEED).cuda()
+    plan = model.compile_inference(x, dtype=torch.float16, streams=1, graph=False, precise=precise).plan
+    assert plan.precise == precise
+    nlev = len(model.levels)
+    with torch.no_grad(), torch.cuda.device(x.device):
+        plan.forward(x)                                   # warm: weights packed, workspaces sized
+        whole = plan._forward_one(x).clone()
+        assert torch.equal(whole, plan.forward(x))
+        for k in range(1, nlev):
+            mid = plan._forward_one(x, 0, k)
+            assert isinstance(mid, tuple) == precise
+            assert torch.equal(plan._forward_one(mid, k, None), whole), f"split in front of level {k}"
+    assert _native_loaded()

@@ -113,3 +113,26 @@ def test_stored_streams_cost_more_than_rounded_operands():
     precise = err(mid="r", stem0="r")                          # what the precise plan still rounds once: operands only
     print(f"stored streams {stored:.2e}, one operand {operand:.2e}, 16-bit plan {plan16:.2e}, precise plan {precise:.2e}")
     assert stored > 3 * operand and precise < 0.5 * plan16   # tiny_hier (stress weights): 1.0e-3 vs 1.7e-4; 2.8e-4 vs 9.5e-4 (FasterViT-4: 1.3e-4 vs 6.7e-4)
+
+
+def test_plan_options_are_declared_and_conv_weights_are_named(monkeypatch):
+    """Every option bench.py and inference.py set on a plan is a real attribute of a fresh ``DeployPlan`` with its documented default (a misspelt
+    option then fails instead of silently being the default), and ``_cw`` reads the same by field name and by position."""
+    for env in ("FVIT_DOWN_WEIGHT_TERMS", "FVIT_PRECISE_DEPLOY"):   # the defaults below are those of an environment without the switches
+        monkeypatch.delenv(env, raising=False)
+    m, _ = _model("tiny_hier")
+    plan = DeployPlan(m, torch.float16)
+    want = dict(streams=1, join_from=None, slot_base=0, shard_sizes=None, serialize_shards=False, down_weight_terms=1, precise=False, sig=None,
+                _warm_geometries=set())
+    for name, default in want.items():
+        assert name in vars(plan), name
+        assert vars(plan)[name] == default and type(vars(plan)[name]) is type(default), name
+    blk = m.levels[0].blocks[0]
+    wa, _ = _fold(blk.conv1, blk.norm1)
+    for terms in (1, 2):
+        w = plan._cw(wa, terms=terms)
+        assert w._fields == ("wcl", "wk", "wband", "terms", "cv", "wk_classic")
+        wcl, wk, wband, wt, cv, wk_classic = w
+        for by_name, by_pos in zip((w.wcl, w.wk, w.wband, w.terms, w.cv, w.wk_classic), (wcl, wk, wband, wt, cv, wk_classic)):
+            assert by_name is by_pos
+        assert w.terms == terms and w[3] == terms and w.wk is w[1] and w.wk is not None
