@@ -118,6 +118,9 @@ extern "C" int fvit_attention_spad(int32_t S);
 
 struct StageLayout {
     int nW, nloc, ncw, S, G;
+    int rpi;                 // window-tensor rows per image
+    int at;                  // activation terms: weight_terms 3 ("x3") keeps [hi | lo] images in every 16-bit activation row (stride at x ld*, lo at column ld*)
+    float scale;             // softmax scale
     int64_t Mx, Mc;          // window-tensor rows, carrier rows
     int ldn, ldqkv, ldao, ldh;
     size_t off_X, off_Xn, off_QKV, off_AO, off_H, off_R, off_Rn, off_RQKV, off_RAO, off_RH, off_SLAB, off_CNT, off_SPLITK, splitk_bytes, total;
@@ -136,6 +139,9 @@ static bool make_layout(const FvitStageDesc& d, StageLayout& L) {
     L.ncw = d.hier ? d.cw * d.cw : 0;
     L.S = L.nloc + L.ncw;
     L.G = L.ncw * L.nW;
+    L.rpi = L.nW * L.S;
+    L.at = d.weight_terms == 3 ? 2 : 1;
+    L.scale = d.qk_scale > 0.f ? d.qk_scale : 1.0f / sqrtf((float)(d.C / d.heads));
     L.Mx = (int64_t)d.batch * L.nW * L.S;
     L.Mc = (int64_t)d.batch * L.G;
     L.ldn = round_up(d.C, FVIT_TILE_K);
@@ -146,8 +152,7 @@ static bool make_layout(const FvitStageDesc& d, StageLayout& L) {
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
     L.off_X = take((size_t)L.Mx * d.C * 4);
-    // weight_terms 3 ("x3"): every 16-bit activation row holds TWO terms [hi | lo] (row stride 2 x ld*, lo image at column ld*)
-    const size_t at = d.weight_terms == 3 ? 2 : 1;
+    const size_t at = L.at;
     L.off_Xn = take((size_t)Mxp * L.ldn * 2 * at);
     L.off_QKV = take((size_t)Mxp * L.ldqkv * 2 * at);
     L.off_AO = take((size_t)Mxp * L.ldao * 2 * at);
@@ -201,247 +206,361 @@ static bool make_layout(const FvitStageDesc& d, StageLayout& L) {
         if (rc__ != FVIT_OK) return rc__; \
     } while (0)
 
-// LayerNorm folded into the following Linear's A staging (fvit_lngemm.hip): C = 256 / 512 and launches small enough that the separate
-// LayerNorm kernel is a dispatch-floor launch of its own (carrier-token branch, stage 3, shard-sized launches).  OPT-IN (fvit_tune
-// "ln_gemm" = 1): measured r02 it removes 17-22 launches per stream shard but LOSES end to end (60.9k vs 74.3k images/s): its
-// resident operand panel needs 96-128 KiB of LDS per workgroup, so no other stream shard's kernel can share the CU with it -- and
-// that co-residency is what the stream shards' gain comes from (profiles/r02_ln_gemm_ab.log)
-static bool use_ln_gemm(const FvitStageDesc& d, int N, int ldw, int ldo, int64_t rows) {
-    return d.weight_terms == 1 && ln_gemm_supported(d.C, N, ldw, ldo) && tune_get("ln_gemm", 0) && rows <= tune_get("ln_gemm_max_rows", 16384);
+// ------------------------------------------------------------------------------------------
+// call-struct builders: the one place that maps the flat argument order of the C ABI (and of the stage driver) onto the
+// positional fields of the fused kernels' call structs; callers set the optional trailing fields (terms, slab, ts) by name
+// ------------------------------------------------------------------------------------------
+static AttnBlkCall attnblk_call(int dtype, const float* srcA, int rowsA, const float* srcB, int rowsB, const int32_t* src_idx,
+                                const int32_t* add_idx, const float* add, const float* ln_w, const float* ln_b, float eps, int rows_per_image,
+                                const void* w_qkv_frag, const float* b_qkv_heads, const void* w_proj_frag, const float* b_proj,
+                                const float* gamma, const float* bias, float* x_out, int nwin, int S, int heads, int C, float scale) {
+    return {dtype, srcA, rowsA, srcB, rowsB, src_idx, add_idx, add, ln_w, ln_b, eps, rows_per_image, w_qkv_frag,
+            b_qkv_heads, w_proj_frag, b_proj, gamma, bias, x_out, nwin, S, heads, C, scale};
 }
 
-// LN -> qkv -> attention -> proj + gamma-residual, on `rows` rows of the f32 stream `x`
-static int run_attn(const FvitStageDesc& d, const StageLayout& L, const FvitAttnWeights& w, float* x, int64_t rows, void* xn,
-                    void* qkv, void* ao, int nwin, int S, bool ln_done, hipStream_t st, bool qkv_done = false, char* wsb = nullptr) {
+static MlpFusedCall mlp_fused_call(int dtype, float* x, int M, int C, int hidden, const float* ln_w, const float* ln_b, float eps,
+                                   const void* w_fc1_frag, const float* b_fc1, const void* w_fc2_frag, const float* b_fc2, const float* gamma) {
+    return {dtype, x, M, C, hidden, ln_w, ln_b, eps, w_fc1_frag, b_fc1, w_fc2_frag, b_fc2, gamma};
+}
+
+static CtBlkCall ctblk_call(int dtype, const float* X, int rowsA, const int32_t* src_idx, const float* add, float* R, int batch, int G,
+                            int heads, int C, int hidden, const float* ln1_w, const float* ln1_b, const void* w_qkv_frag,
+                            const float* b_qkv_heads, const void* w_proj_frag, const float* b_proj, const float* gamma1, const float* bias,
+                            float scale, const float* ln2_w, const float* ln2_b, const void* w_fc1_frag, const float* b_fc1,
+                            const void* w_fc2_frag, const float* b_fc2, const float* gamma2, float eps) {
+    return {dtype, X, rowsA, src_idx, add, R, batch, G, heads, C, hidden, ln1_w, ln1_b, w_qkv_frag, b_qkv_heads, w_proj_frag,
+            b_proj, gamma1, bias, scale, ln2_w, ln2_b, w_fc1_frag, b_fc1, w_fc2_frag, b_fc2, gamma2, eps};
+}
+
+// ------------------------------------------------------------------------------------------
+// block routes: which kernel runs each sub-block.  choose_route is the only place that asks; run_block executes the answer.
+// ------------------------------------------------------------------------------------------
+enum class CarrierRoute {
+    NONE,           // local-only stage
+    FUSED_CT,       // the whole carrier branch, attention and MLP, in one kernel (fvit_ctblk.hip)
+    ATTNBLK,        // fused attention sub-block (fvit_attnblk.hip), then the MLP route
+    LNGEMM_CHAIN,   // gather + hat_norm1 + qkv in one kernel (fvit_lngemm.hip), attention, proj, then the MLP route
+    CHAIN,          // gather-LayerNorm, qkv, attention, proj, then the MLP route
+};
+enum class WinAttnRoute {
+    WINBLK,            // fvit_winblk.hip
+    ATTNBLK,           // fvit_attnblk.hip / fvit_attnblk2.hip
+    LNGEMM_PREADDED,   // the previous block's fc2 epilogue added this block's position embedding: norm1 + qkv in one kernel, attention, proj
+    CHAIN,             // gather-LayerNorm, qkv, attention, proj
+};
+enum class MlpRoute {
+    WINMLP,         // fvit_winmlp.hip
+    MLP_FUSED,      // fvit_mlp.hip
+    LNGEMM_CHAIN,   // norm2 + fc1 + GELU in one kernel, fc2
+    CHAIN,          // LayerNorm, fc1 + GELU, fc2
+};
+
+struct BlockRoute {
+    CarrierRoute carrier = CarrierRoute::NONE;
+    MlpRoute carrier_mlp = MlpRoute::CHAIN;   // unused with CarrierRoute::NONE / FUSED_CT
+    WinAttnRoute window_attn = WinAttnRoute::CHAIN;
+    MlpRoute window_mlp = MlpRoute::CHAIN;
+    // Local-only stages (no carrier tokens: stage 3 of FasterViT-0) with the LayerNorm-in-GEMM kernels: the in-place `x = x + pos_embed`
+    // of block i + 1 (AR:671) is applied by block i's fc2 epilogue, so block i + 1's norm1 is a plain LayerNorm of X and folds into its
+    // qkv GEMM.  Same two fp32 additions in the same order as the separate kernel (bitwise the same residual stream).
+    // Only the two chain forms of window_mlp have that epilogue and only a chain window_attn has a norm1 to fold, so only a block whose
+    // window routes are both chains is eligible; the stage entry pairs eligible neighbours: block i gets pe_next, block i + 1 LNGEMM_PREADDED.
+    bool preadd_eligible = false;
+    const float* pe_next = nullptr;   // position-embedding rows of block i + 1 for this block's fc2 epilogue, or null
+    int win_blk_split = 1, win_mlp_split = 1;   // C = 512: workgroups that share a window's heads / a 64-row group's hidden units
+};
+
+// The knobs that select a route, read once by every stage / block call: fvit_tune takes effect from the next call on, nothing is cached
+struct RouteKnobs {
+    const int ln_gemm = tune_get("ln_gemm", 0), ln_gemm_max_rows = tune_get("ln_gemm_max_rows", 16384);
+    const int attn_fused = tune_get("attn_fused", 1), attn_fused_x2 = tune_get("attn_fused_x2", 1);
+    const int attn_fused_min_rows = tune_get("attn_fused_min_rows", 16384), attn_fused512_min_rows = tune_get("attn_fused512_min_rows", 1 << 30);
+    const int mlp_fused = tune_get("mlp_fused", 1);
+    const int mlp_fused_min_rows = tune_get("mlp_fused_min_rows", 16384), mlp_fused512_min_rows = tune_get("mlp_fused512_min_rows", 1 << 30);
+    const int win_mlp = tune_get("win_mlp", 1), win_mlp256 = tune_get("win_mlp256", 2), win_mlp_split = tune_get("win_mlp_split", 1);
+    const int win_fused = tune_get("win_fused", 1), win_fused256 = tune_get("win_fused256", 0), win_blk_split = tune_get("win_blk_split", 1);
+    const int ct_fused = tune_get("ct_fused", 1), pe_preadd = tune_get("pe_preadd", 1);
+};
+
+static BlockRoute choose_route(const FvitStageDesc& d, const StageLayout& L, const FvitBlockWeights& w, const RouteKnobs& k) {
+    const int T = d.weight_terms;
+    // LayerNorm folded into the following Linear's A staging (fvit_lngemm.hip): C = 256 / 512 and launches small enough that the separate
+    // LayerNorm kernel is a dispatch-floor launch of its own (carrier-token branch, stage 3, shard-sized launches).  OPT-IN (fvit_tune
+    // "ln_gemm" = 1): measured r02 it removes 17-22 launches per stream shard but LOSES end to end (60.9k vs 74.3k images/s): its
+    // resident operand panel needs 96-128 KiB of LDS per workgroup, so no other stream shard's kernel can share the CU with it -- and
+    // that co-residency is what the stream shards' gain comes from (profiles/r02_ln_gemm_ab.log)
+    auto ln_gemm_ok = [&](int N, int ldo, int64_t rows) {
+        return T == 1 && ln_gemm_supported(d.C, N, L.ldn, ldo) && k.ln_gemm && rows <= k.ln_gemm_max_rows;
+    };
+    // the fused attention block wins once the launch fills the chip (92 vs 117 us at 54k rows); on the carrier branch (4k rows,
+    // 32 workgroups) it is latency-bound and loses (38 vs 30 us)
+    // C = 512 / 16 heads (stage 3): the fused instance is correct but loses end to end (66.0k vs 71.9k images/s, r01 sweep r41): one
+    // workgroup per 49-token window streams 2 MiB of weights for 49 rows => opt-in (attn_fused512_min_rows)
+    auto attnblk = [&](const FvitAttnWeights& a, int S, int64_t rows) {
+        // two-term weights (r04): the C = 256 window instance takes them ([hi image | lo image] fragment arrays); fvit_tune "attn_fused_x2" = 0 restores the r03 chain
+        const bool terms_ok = T == 1 || (T == 2 && d.C == 256 && S > 48 && k.attn_fused_x2);
+        return terms_ok && a.w_qkv_frag && a.b_qkv_heads && a.w_proj_frag && d.dpad == 32 && d.C / d.heads == 32 && attnblk_supported(d.C, d.heads, S) &&
+               rows >= (d.C == 256 ? k.attn_fused_min_rows : k.attn_fused512_min_rows) && k.attn_fused;
+    };
+    auto mlp = [&](const FvitMlpWeights& m, int64_t rows) {
+        const bool frags = m.w_fc1_frag && m.w_fc2_frag;
+        // C = 512 (stage 3 of FasterViT-0): 64-row workgroups whose waves split hidden units / output channels (fvit_winmlp.hip)
+        // C = 256: 4-wave 64-row workgroups, two per CU (win_mlp256 = 0: fvit_mlp_fused's kernel)
+        if (T <= 2 && frags && winmlp_supported(d.C, d.hidden) && (d.C == 512 ? k.win_mlp != 0 : rows >= k.mlp_fused_min_rows && k.win_mlp256 != 0))
+            return MlpRoute::WINMLP;
+        // the fused kernel streams all MLP weights per 128-row workgroup: it wins once the launch fills the chip
+        // (>= ~16k rows; 104 vs 137 us at 54k rows) and loses on the latency-bound carrier branch (4k rows: 83 vs 31 us)
+        // C = 512 (stage 3): the fused instance is correct but slower than LN + 2 GEMMs at these row counts (65-196 workgroups, each
+        // streaming 4 MiB of weights: 65.8k vs 71.0k images/s end to end, r01 sweep r31) => opt-in
+        if (T == 1 && frags && mlp_fused_supported(d.C, d.hidden) && rows >= (d.C == 256 ? k.mlp_fused_min_rows : k.mlp_fused512_min_rows) && k.mlp_fused)
+            return MlpRoute::MLP_FUSED;
+        return ln_gemm_ok(d.hidden, L.ldh, rows) ? MlpRoute::LNGEMM_CHAIN : MlpRoute::CHAIN;
+    };
+
+    BlockRoute r;
+    r.win_blk_split = k.win_blk_split;
+    r.win_mlp_split = k.win_mlp_split;
+    if (d.hier) {
+        const FvitAttnWeights& a = w.hat_attn;
+        if (T <= 2 && ctblk_supported(d.C, d.heads, L.G, d.hidden) && d.dpad == 32 && a.w_qkv_frag && a.b_qkv_heads && a.w_proj_frag && a.bias &&
+            w.hat_mlp.w_fc1_frag && w.hat_mlp.w_fc2_frag && k.ct_fused)
+            r.carrier = CarrierRoute::FUSED_CT;
+        else if (attnblk(a, L.G, L.Mc))
+            r.carrier = CarrierRoute::ATTNBLK;
+        else
+            r.carrier = ln_gemm_ok(L.ldqkv, L.ldqkv, L.Mc) ? CarrierRoute::LNGEMM_CHAIN : CarrierRoute::CHAIN;
+        r.carrier_mlp = mlp(w.hat_mlp, L.Mc);
+    }
+    // C = 512 (stage 3 of FasterViT-0): the attention sub-block with the waves of a window splitting heads / output channels (fvit_winblk.hip)
+    // C = 256: the 4-wave form, two workgroups per CU (opt-in)
+    const FvitAttnWeights& a = w.attn;
+    if (T <= 2 && (T == 1 || d.C == 512) && winblk_supported(d.C, d.heads, L.S) && d.dpad == 32 && a.w_qkv_frag && a.b_qkv_heads && a.w_proj_frag && a.bias &&
+        (d.C == 512 ? k.win_fused != 0 : k.win_fused256 != 0))
+        r.window_attn = WinAttnRoute::WINBLK;
+    else if (attnblk(a, L.S, L.Mx))
+        r.window_attn = WinAttnRoute::ATTNBLK;
+    r.window_mlp = mlp(w.mlp, L.Mx);
+    r.preadd_eligible = !d.hier && r.window_attn == WinAttnRoute::CHAIN && (r.window_mlp == MlpRoute::CHAIN || r.window_mlp == MlpRoute::LNGEMM_CHAIN) &&
+                        ln_gemm_ok(L.ldqkv, L.ldqkv, L.Mx) && k.pe_preadd;
+    return r;
+}
+
+// ------------------------------------------------------------------------------------------
+// block executor
+// ------------------------------------------------------------------------------------------
+struct Branch {   // one token branch of a block: its fp32 residual stream and 16-bit scratch rows in the workspace
+    float* x;
+    int64_t rows;
+    void *xn, *qkv, *ao, *h;
+    int nwin, S;   // attention geometry
+};
+
+// LayerNorm of `rows` plain rows of `src` into n_out; a gathering caller sets the source / add / x_out fields on top
+static LnCall ln_call(const FvitStageDesc& d, const StageLayout& L, const float* ln_w, const float* ln_b, const float* src, int64_t rows, void* n_out) {
+    LnCall ln = {d.operand_dtype, src, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, n_out, L.at * L.ldn, ln_w, ln_b, 1e-5f, (int)rows, 1, d.C};
+    if (L.at == 2) ln.lo_off = L.ldn;
+    return ln;
+}
+
+enum class AttnStart { QKV_GEMM, CORE };   // CORE: a LayerNorm-in-GEMM launch has written b.qkv already
+
+// qkv (from the LayerNorm rows b.xn) -> attention -> proj + gamma-residual into b.x
+static int run_attn(const FvitStageDesc& d, const StageLayout& L, const FvitAttnWeights& w, AttnStart start, const Branch& b, char* ws, hipStream_t st) {
     const int dt = d.operand_dtype;
     const int T = d.weight_terms;   // K-concatenated weight terms: the GEMMs run K = T x ld against the activation columns (GemmCall.ka)
-    const int AT = T == 3 ? 2 : 1;  // activation terms: rows of xn / qkv / ao hold [hi | lo] images (stride AT x ld, lo at column ld)
-    if (!ln_done && !qkv_done) {
-        LnCall ln = {dt, x, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, xn, AT * L.ldn, w.ln_w, w.ln_b, 1e-5f, (int)rows, 1, d.C};
-        if (AT == 2) ln.lo_off = L.ldn;
-        FVIT_TRY(launch_gather_layernorm(ln, st));
-    }
-    dbg_rowhash("attn.xn", xn, rows, AT * L.ldn * 2, st);
-    if (!qkv_done) {
-        GemmCall g1 = {dt, xn, AT * L.ldn, w.w_qkv, T * L.ldn, w.b_qkv, nullptr, qkv, AT * L.ldqkv, (int)rows, L.ldqkv, T * L.ldn, 0};
+    const int AT = L.at;
+    dbg_rowhash("attn.xn", b.xn, b.rows, AT * L.ldn * 2, st);
+    if (start == AttnStart::QKV_GEMM) {
+        GemmCall g1 = {dt, b.xn, AT * L.ldn, w.w_qkv, T * L.ldn, w.b_qkv, nullptr, b.qkv, AT * L.ldqkv, (int)b.rows, L.ldqkv, T * L.ldn, 0};
         g1.ka = L.ldn;
         if (AT == 2) g1.out_lo_off = L.ldqkv;
         FVIT_TRY(launch_gemm(g1, st));
     }
-    dbg_rowhash("attn.qkv", qkv, rows, AT * L.ldqkv * 2, st);
-    const float scale = (d.qk_scale > 0.f ? d.qk_scale : 1.0f / sqrtf((float)(d.C / d.heads)));
-    AttnCall at = {dt, qkv, AT * L.ldqkv, ao, AT * L.ldao, w.bias, nwin, S, d.heads, d.dpad, scale, w.rel_table, w.rel_w, w.rel_ng, d.C / d.heads};
+    dbg_rowhash("attn.qkv", b.qkv, b.rows, AT * L.ldqkv * 2, st);
+    AttnCall at = {dt, b.qkv, AT * L.ldqkv, b.ao, AT * L.ldao, w.bias, b.nwin, b.S, d.heads, d.dpad, L.scale, w.rel_table, w.rel_w, w.rel_ng, d.C / d.heads};
     if (AT == 2) { at.q_lo_off = L.ldqkv; at.o_lo_off = L.ldao; }
     FVIT_TRY(launch_attention(at, st));
-    dbg_rowhash("attn.ao", ao, rows, AT * L.ldao * 2, st);
-    GemmCall g2 = {dt, ao, AT * L.ldao, w.w_proj, T * L.ldao, w.b_proj, w.gamma, x, d.C, (int)rows, d.C, T * L.ldao, 2};
+    dbg_rowhash("attn.ao", b.ao, b.rows, AT * L.ldao * 2, st);
+    GemmCall g2 = {dt, b.ao, AT * L.ldao, w.w_proj, T * L.ldao, w.b_proj, w.gamma, b.x, d.C, (int)b.rows, d.C, T * L.ldao, 2};
     g2.ka = L.ldao;
-    if (wsb && L.splitk_bytes) { g2.splitk_slab = (float*)(wsb + L.off_SPLITK); g2.splitk_bytes = L.splitk_bytes; }
+    if (L.splitk_bytes) { g2.splitk_slab = (float*)(ws + L.off_SPLITK); g2.splitk_bytes = L.splitk_bytes; }
     FVIT_TRY(launch_gemm(g2, st));
-    dbg_rowhash("attn.out", x, rows, d.C * 4, st);
+    dbg_rowhash("attn.out", b.x, b.rows, d.C * 4, st);
     return FVIT_OK;
 }
 
-// the fused attention block wins once the launch fills the chip (92 vs 117 us at 54k rows); on the carrier branch (4k rows,
-// 32 workgroups) it is latency-bound and loses (38 vs 30 us)
-// C = 512 / 16 heads (stage 3): the fused instance is correct but loses end to end (66.0k vs 71.9k images/s, r01 sweep r41): one
-// workgroup per 49-token window streams 2 MiB of weights for 49 rows => opt-in (attn_fused512_min_rows)
-static bool fused_attn_ok(const FvitStageDesc& d, const FvitAttnWeights& w, int S, int64_t rows) {
-    // two-term weights (r04): the C = 256 window instance takes them ([hi image | lo image] fragment arrays); fvit_tune "attn_fused_x2" = 0 restores the r03 chain
-    const bool terms_ok = d.weight_terms == 1 || (d.weight_terms == 2 && d.C == 256 && S > 48 && tune_get("attn_fused_x2", 1));
-    return terms_ok && w.w_qkv_frag && w.b_qkv_heads && w.w_proj_frag && d.dpad == 32 && d.C / d.heads == 32 && attnblk_supported(d.C, d.heads, S) &&
-           rows >= (d.C == 256 ? tune_get("attn_fused_min_rows", 16384) : tune_get("attn_fused512_min_rows", 1 << 30)) && tune_get("attn_fused", 1);
-}
-
-// LN -> fc1 + GELU -> fc2 + gamma-residual
-struct NextPe {   // position-embedding rows of the NEXT block, applied in this block's fc2 epilogue (window branch, local-only stages)
-    const float* add = nullptr;
-    const int32_t* add_idx = nullptr;
-    int rows_per_image = 1;
-};
-
-static bool win_mlp_ok(const FvitStageDesc& d, const FvitMlpWeights& w, int64_t rows) {
-    if (d.weight_terms > 2 || !winmlp_supported(d.C, d.hidden) || !w.w_fc1_frag || !w.w_fc2_frag) return false;
-    if (d.C == 512) return tune_get("win_mlp", 1) != 0;
-    return rows >= tune_get("mlp_fused_min_rows", 16384) && tune_get("win_mlp256", 2) != 0;   // C = 256: 4-wave 64-row workgroups, two per CU (0: fvit_mlp_fused's kernel)
-}
-
-static bool mlp_takes_fused_kernel(const FvitStageDesc& d, const FvitMlpWeights& w, int64_t rows) {
-    if (d.weight_terms != 1) return false;
-    const int64_t fused_min = d.C == 256 ? tune_get("mlp_fused_min_rows", 16384) : tune_get("mlp_fused512_min_rows", 1 << 30);
-    return w.w_fc1_frag && w.w_fc2_frag && mlp_fused_supported(d.C, d.hidden) && rows >= fused_min && tune_get("mlp_fused", 1);
-}
-
-static int run_mlp(const FvitStageDesc& d, const StageLayout& L, const FvitMlpWeights& w, float* x, int64_t rows, void* xn, void* h,
-                   hipStream_t st, const NextPe* next_pe = nullptr, char* slab = nullptr) {
+// LN -> fc1 + GELU -> fc2 + gamma-residual into b.x.  r.pe_next goes into the fc2 epilogue of the chain forms; it is set on local-only
+// stages alone (BlockRoute), so the carrier branch never sees it
+static int run_mlp(const FvitStageDesc& d, const StageLayout& L, const FvitMlpWeights& w, MlpRoute route, const BlockRoute& r, const Branch& b,
+                   const FvitStageTables& t, char* ws, hipStream_t st) {
     const int dt = d.operand_dtype;
-    const int T = d.weight_terms;
-    // the fused kernel streams all MLP weights per 128-row workgroup: it wins once the launch fills the chip
-    // (>= ~16k rows; 104 vs 137 us at 54k rows) and loses on the latency-bound carrier branch (4k rows: 83 vs 31 us)
-    // C = 512 (stage 3): the fused instance is correct but slower than LN + 2 GEMMs at these row counts (65-196 workgroups, each
-    // streaming 4 MiB of weights: 65.8k vs 71.0k images/s end to end, r01 sweep r31) => opt-in
-    if (win_mlp_ok(d, w, rows)) {
-        // C = 512 (stage 3 of FasterViT-0): 64-row workgroups whose waves split hidden units / output channels (fvit_winmlp.hip)
-        if (next_pe && next_pe->add) { set_error("internal: position-embedding pre-add requested on the fused MLP path"); return FVIT_EINVAL; }
-        MlpFusedCall mc = {dt, x, (int)rows, d.C, d.hidden, w.ln_w, w.ln_b, 1e-5f, w.w_fc1_frag, w.b_fc1, w.w_fc2_frag, w.b_fc2, w.gamma, T};
-        if (slab && L.off_SLAB && rows <= L.Mx) {   // window branch of a C = 512 stage: hidden units split over sibling workgroups
-            mc.slab = (float*)(slab + L.off_SLAB);
-            mc.counters = (int*)(slab + L.off_CNT);
-            mc.nsplit = tune_get("win_mlp_split", 1);
+    const int T = d.weight_terms, AT = L.at;
+    switch (route) {
+    case MlpRoute::WINMLP: {
+        MlpFusedCall mc = mlp_fused_call(dt, b.x, (int)b.rows, d.C, d.hidden, w.ln_w, w.ln_b, 1e-5f, w.w_fc1_frag, w.b_fc1, w.w_fc2_frag, w.b_fc2, w.gamma);
+        mc.terms = T;
+        if (L.off_SLAB) {   // C = 512 stage (either branch: Mc <= Mx): hidden units split over sibling workgroups
+            mc.slab = (float*)(ws + L.off_SLAB);
+            mc.counters = (int*)(ws + L.off_CNT);
+            mc.nsplit = r.win_mlp_split;
         }
         FVIT_TRY(launch_winmlp(mc, st));
-        dbg_rowhash("winmlp.out", x, rows, d.C * 4, st);
+        dbg_rowhash("winmlp.out", b.x, b.rows, d.C * 4, st);
         return FVIT_OK;
     }
-    if (mlp_takes_fused_kernel(d, w, rows)) {
-        if (next_pe && next_pe->add) { set_error("internal: position-embedding pre-add requested on the fused MLP path"); return FVIT_EINVAL; }
-        MlpFusedCall mc = {dt, x, (int)rows, d.C, d.hidden, w.ln_w, w.ln_b, 1e-5f, w.w_fc1_frag, w.b_fc1, w.w_fc2_frag, w.b_fc2, w.gamma};
-        dbg_rowhash("mlpf.in", x, rows, d.C * 4, st);
+    case MlpRoute::MLP_FUSED: {
+        MlpFusedCall mc = mlp_fused_call(dt, b.x, (int)b.rows, d.C, d.hidden, w.ln_w, w.ln_b, 1e-5f, w.w_fc1_frag, w.b_fc1, w.w_fc2_frag, w.b_fc2, w.gamma);
+        dbg_rowhash("mlpf.in", b.x, b.rows, d.C * 4, st);
         FVIT_TRY(launch_mlp_fused(mc, st));
-        dbg_rowhash("mlpf.out", x, rows, d.C * 4, st);
+        dbg_rowhash("mlpf.out", b.x, b.rows, d.C * 4, st);
         return FVIT_OK;
     }
-    const int AT = T == 3 ? 2 : 1;   // activation terms (see run_attn)
-    LnCall ln = {dt, x, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, xn, AT * L.ldn, w.ln_w, w.ln_b, 1e-5f, (int)rows, 1, d.C};
-    if (AT == 2) ln.lo_off = L.ldn;
-    if (use_ln_gemm(d, d.hidden, L.ldn, L.ldh, rows)) {
+    case MlpRoute::LNGEMM_CHAIN: {
         // norm2 -> fc1 -> GELU in one kernel (AR:697 with AR:401-403): the normalised rows never reach HBM
-        LnGemmCall lg = {ln, w.w_fc1, L.ldn, w.b_fc1, h, L.ldh, d.hidden, 1};
+        LnGemmCall lg = {ln_call(d, L, w.ln_w, w.ln_b, b.x, b.rows, b.xn), w.w_fc1, L.ldn, w.b_fc1, b.h, L.ldh, d.hidden, 1};
         FVIT_TRY(launch_ln_gemm(lg, st));
-    } else {
-        FVIT_TRY(launch_gather_layernorm(ln, st));
-        GemmCall g1 = {dt, xn, AT * L.ldn, w.w_fc1, T * L.ldn, w.b_fc1, nullptr, h, AT * L.ldh, (int)rows, d.hidden, T * L.ldn, 1};
+        break;
+    }
+    case MlpRoute::CHAIN: {
+        FVIT_TRY(launch_gather_layernorm(ln_call(d, L, w.ln_w, w.ln_b, b.x, b.rows, b.xn), st));
+        GemmCall g1 = {dt, b.xn, AT * L.ldn, w.w_fc1, T * L.ldn, w.b_fc1, nullptr, b.h, AT * L.ldh, (int)b.rows, d.hidden, T * L.ldn, 1};
         g1.ka = L.ldn;
         if (AT == 2) g1.out_lo_off = L.ldh;
         FVIT_TRY(launch_gemm(g1, st));
+        break;
     }
-    dbg_rowhash("mlp.h", h, rows, AT * L.ldh * 2, st);
-    GemmCall g2 = {dt, h, AT * L.ldh, w.w_fc2, T * L.ldh, w.b_fc2, w.gamma, x, d.C, (int)rows, d.C, T * L.ldh, 2};
+    }
+    dbg_rowhash("mlp.h", b.h, b.rows, AT * L.ldh * 2, st);
+    GemmCall g2 = {dt, b.h, AT * L.ldh, w.w_fc2, T * L.ldh, w.b_fc2, w.gamma, b.x, d.C, (int)b.rows, d.C, T * L.ldh, 2};
     g2.ka = L.ldh;
-    if (next_pe && next_pe->add) { g2.add = next_pe->add; g2.add_idx = next_pe->add_idx; g2.rows_per_image = next_pe->rows_per_image; }
-    if (slab && L.splitk_bytes) { g2.splitk_slab = (float*)(slab + L.off_SPLITK); g2.splitk_bytes = L.splitk_bytes; }
+    if (r.pe_next) { g2.add = r.pe_next; g2.add_idx = t.ln1_add; g2.rows_per_image = L.rpi; }
+    if (L.splitk_bytes) { g2.splitk_slab = (float*)(ws + L.off_SPLITK); g2.splitk_bytes = L.splitk_bytes; }
     FVIT_TRY(launch_gemm(g2, st));
-    dbg_rowhash("mlp.out", x, rows, d.C * 4, st);
+    dbg_rowhash("mlp.out", b.x, b.rows, d.C * 4, st);
     return FVIT_OK;
 }
 
-// Local-only stages (no carrier tokens: stage 3 of FasterViT-0) with the LayerNorm-in-GEMM kernels: the in-place `x = x + pos_embed`
-// of block i + 1 (AR:671) is applied by block i's fc2 epilogue, so block i + 1's norm1 is a plain LayerNorm of X and folds into its
-// qkv GEMM.  Same two fp32 additions in the same order as the separate kernel (bitwise the same residual stream).
-// C = 512 (stage 3 of FasterViT-0): the attention sub-block with the waves of a window splitting heads / output channels (fvit_winblk.hip)
-static bool win_fused_ok(const FvitStageDesc& d, const FvitAttnWeights& w, int S) {
-    if (d.weight_terms > 2 || (d.weight_terms != 1 && d.C != 512) || !winblk_supported(d.C, d.heads, S) || d.dpad != 32 || !w.w_qkv_frag || !w.b_qkv_heads || !w.w_proj_frag || !w.bias) return false;
-    return d.C == 512 ? tune_get("win_fused", 1) != 0 : tune_get("win_fused256", 0) != 0;   // C = 256: the 4-wave form, two workgroups per CU
+// the window branch's gather + norm1 + qkv + attention + proj + gamma3-residual -> X in one kernel, for launch_winblk and launch_attnblk alike
+static AttnBlkCall window_attnblk_call(const FvitStageDesc& d, const StageLayout& L, const FvitBlockWeights& w, const FvitStageTables& t, float* X, float* R) {
+    const FvitAttnWeights& a = w.attn;
+    AttnBlkCall ab = attnblk_call(d.operand_dtype, X, L.rpi, R, L.G, (d.hier ? t.ln1_src : nullptr), t.ln1_add, w.pe_x, a.ln_w, a.ln_b, 1e-5f, L.rpi,
+                                  a.w_qkv_frag, a.b_qkv_heads, a.w_proj_frag, a.b_proj, a.gamma, a.bias, X, d.batch * L.nW, L.S, d.heads, d.C, L.scale);
+    ab.terms = d.weight_terms;
+    return ab;
 }
 
-static bool pe_preadd_chain(const FvitStageDesc& d, const StageLayout& L, const FvitBlockWeights& w) {
-    return !d.hier && !win_fused_ok(d, w.attn, L.S) && !win_mlp_ok(d, w.mlp, L.Mx) && use_ln_gemm(d, L.ldqkv, L.ldn, L.ldqkv, L.Mx) && !fused_attn_ok(d, w.attn, L.S, L.Mx) && !mlp_takes_fused_kernel(d, w.mlp, L.Mx) &&
-           tune_get("pe_preadd", 1);
-}
-
-static int run_block(const FvitStageDesc& d, const StageLayout& L, const FvitBlockWeights& w, const FvitStageTables& t, char* ws,
-                     hipStream_t st, bool pe_preadded = false, const NextPe* next_pe = nullptr) {
+// One block in the launch order at the top of this file, each sub-block on the kernel its route names
+static int run_block(const FvitStageDesc& d, const StageLayout& L, const BlockRoute& r, const FvitBlockWeights& w, const FvitStageTables& t,
+                     char* ws, hipStream_t st) {
     const int dt = d.operand_dtype;
     float* X = (float*)(ws + L.off_X);
-    void* Xn = ws + L.off_Xn;
-    void* QKV = ws + L.off_QKV;
-    void* AO = ws + L.off_AO;
-    void* Hb = ws + L.off_H;
     float* R = (float*)(ws + L.off_R);
-    const int rpi = L.nW * L.S;  // window-tensor rows per image
-    if (d.hier) {
-        void* Rn = ws + L.off_Rn;
-        void* RQKV = ws + L.off_RQKV;
-        void* RAO = ws + L.off_RAO;
-        void* RH = ws + L.off_RH;
-        const float scale = (d.qk_scale > 0.f ? d.qk_scale : 1.0f / sqrtf((float)(d.C / d.heads)));
-        bool ct_done = false;
-        if (d.weight_terms <= 2 && ctblk_supported(d.C, d.heads, L.G, d.hidden) && d.dpad == 32 && w.hat_attn.w_qkv_frag && w.hat_attn.b_qkv_heads && w.hat_attn.w_proj_frag &&
-            w.hat_attn.bias && w.hat_mlp.w_fc1_frag && w.hat_mlp.w_fc2_frag && tune_get("ct_fused", 1)) {
-            // the whole carrier-token branch (AR:679-686) in one kernel, one workgroup per image
-            CtBlkCall cb = {dt, X, rpi, t.ct_src, (d.square ? w.pe_ct : nullptr), R, d.batch, L.G, d.heads, d.C, d.hidden,
-                            w.hat_attn.ln_w, w.hat_attn.ln_b, w.hat_attn.w_qkv_frag, w.hat_attn.b_qkv_heads, w.hat_attn.w_proj_frag, w.hat_attn.b_proj,
-                            w.hat_attn.gamma, w.hat_attn.bias, scale, w.hat_mlp.ln_w, w.hat_mlp.ln_b, w.hat_mlp.w_fc1_frag, w.hat_mlp.b_fc1,
-                            w.hat_mlp.w_fc2_frag, w.hat_mlp.b_fc2, w.hat_mlp.gamma, 1e-5f, d.weight_terms};
-            FVIT_TRY(launch_ctblk(cb, st));
-            ct_done = true;
-            dbg_rowhash("ct.block", R, L.Mc, d.C * 4, st);
-        } else if (fused_attn_ok(d, w.hat_attn, L.G, L.Mc)) {
-            // ct_dewindow gather (+ hat_pos_embed), LN, qkv, attention over the G carrier tokens, proj, gamma1-residual -> R
-            AttnBlkCall ab = {dt, X, rpi, nullptr, 0, t.ct_src, nullptr, (d.square ? w.pe_ct : nullptr), w.hat_attn.ln_w, w.hat_attn.ln_b,
-                              1e-5f, L.G, w.hat_attn.w_qkv_frag, w.hat_attn.b_qkv_heads, w.hat_attn.w_proj_frag, w.hat_attn.b_proj,
-                              w.hat_attn.gamma, w.hat_attn.bias, R, d.batch, L.G, d.heads, d.C, scale};
-            FVIT_TRY(launch_attnblk(ab, st));
-            dbg_rowhash("ct.attnblk", R, L.Mc, d.C * 4, st);
-        } else {
-            // ct_dewindow gather (+ hat_pos_embed) -> R, LN(hat_norm1) -> Rn
-            const int AT = d.weight_terms == 3 ? 2 : 1;
-            LnCall ln = {dt, X, rpi, nullptr, 0, t.ct_src, nullptr, (d.square ? w.pe_ct : nullptr), R, Rn, AT * L.ldn,
-                         w.hat_attn.ln_w, w.hat_attn.ln_b, 1e-5f, (int)L.Mc, L.G, d.C};
-            if (AT == 2) ln.lo_off = L.ldn;
-            if (use_ln_gemm(d, L.ldqkv, L.ldn, L.ldqkv, L.Mc)) {
-                // ct_dewindow gather + hat_pos_embed + hat_norm1 + hat_attn.qkv in one kernel (AR:679-686); R (the fp32 carrier stream)
-                // is written by the kernel's first column group
-                LnGemmCall lg = {ln, w.hat_attn.w_qkv, L.ldn, w.hat_attn.b_qkv, RQKV, L.ldqkv, L.ldqkv, 0};
-                FVIT_TRY(launch_ln_gemm(lg, st));
-                FVIT_TRY(run_attn(d, L, w.hat_attn, R, L.Mc, Rn, RQKV, RAO, d.batch, L.G, true, st, true, ws));
-            } else {
-                FVIT_TRY(launch_gather_layernorm(ln, st));
-                dbg_rowhash("ct.gather", R, L.Mc, d.C * 4, st);
-                FVIT_TRY(run_attn(d, L, w.hat_attn, R, L.Mc, Rn, RQKV, RAO, d.batch, L.G, true, st, false, ws));
-            }
-        }
-        if (!ct_done) FVIT_TRY(run_mlp(d, L, w.hat_mlp, R, L.Mc, Rn, RH, st, nullptr, ws));
+    const Branch win = {X, L.Mx, ws + L.off_Xn, ws + L.off_QKV, ws + L.off_AO, ws + L.off_H, d.batch * L.nW, L.S};
+    const Branch ct = {R, L.Mc, ws + L.off_Rn, ws + L.off_RQKV, ws + L.off_RAO, ws + L.off_RH, d.batch, L.G};
+
+    const FvitAttnWeights& ha = w.hat_attn;
+    const float* pe_ct = d.square ? w.pe_ct : nullptr;
+    // ct_dewindow gather (+ hat_pos_embed) -> R, LN(hat_norm1) -> Rn
+    LnCall ct_ln = ln_call(d, L, ha.ln_w, ha.ln_b, X, L.Mc, ct.xn);
+    ct_ln.rowsA = L.rpi; ct_ln.src_idx = t.ct_src; ct_ln.add = pe_ct; ct_ln.x_out = R; ct_ln.rows_per_image = L.G;
+    switch (r.carrier) {
+    case CarrierRoute::NONE:
+        break;
+    case CarrierRoute::FUSED_CT: {
+        // the whole carrier-token branch (AR:679-686) in one kernel, one workgroup per image
+        const FvitMlpWeights& hm = w.hat_mlp;
+        CtBlkCall cb = ctblk_call(dt, X, L.rpi, t.ct_src, pe_ct, R, d.batch, L.G, d.heads, d.C, d.hidden, ha.ln_w, ha.ln_b, ha.w_qkv_frag,
+                                  ha.b_qkv_heads, ha.w_proj_frag, ha.b_proj, ha.gamma, ha.bias, L.scale, hm.ln_w, hm.ln_b, hm.w_fc1_frag, hm.b_fc1,
+                                  hm.w_fc2_frag, hm.b_fc2, hm.gamma, 1e-5f);
+        cb.terms = d.weight_terms;
+        FVIT_TRY(launch_ctblk(cb, st));
+        dbg_rowhash("ct.block", R, L.Mc, d.C * 4, st);
+        break;
     }
-    if (win_fused_ok(d, w.attn, L.S)) {
-        // C = 512 (stage 3 of FasterViT-0): the same sub-block with the waves of a window splitting heads / output channels
-        const float scale = (d.qk_scale > 0.f ? d.qk_scale : 1.0f / sqrtf((float)(d.C / d.heads)));
-        AttnBlkCall ab = {dt, X, rpi, R, L.G, (d.hier ? t.ln1_src : nullptr), t.ln1_add, w.pe_x, w.attn.ln_w, w.attn.ln_b, 1e-5f, rpi,
-                          w.attn.w_qkv_frag, w.attn.b_qkv_heads, w.attn.w_proj_frag, w.attn.b_proj, w.attn.gamma, w.attn.bias, X,
-                          d.batch * L.nW, L.S, d.heads, d.C, scale};
-        if (L.off_SLAB && d.C == 512) {   // heads of a window split over two sibling workgroups (fvit_tune "win_blk_split" = 2)
+    case CarrierRoute::ATTNBLK: {
+        // ct_dewindow gather (+ hat_pos_embed), LN, qkv, attention over the G carrier tokens, proj, gamma1-residual -> R
+        AttnBlkCall ab = attnblk_call(dt, X, L.rpi, nullptr, 0, t.ct_src, nullptr, pe_ct, ha.ln_w, ha.ln_b, 1e-5f, L.G, ha.w_qkv_frag, ha.b_qkv_heads,
+                                      ha.w_proj_frag, ha.b_proj, ha.gamma, ha.bias, R, d.batch, L.G, d.heads, d.C, L.scale);
+        FVIT_TRY(launch_attnblk(ab, st));
+        dbg_rowhash("ct.attnblk", R, L.Mc, d.C * 4, st);
+        break;
+    }
+    case CarrierRoute::LNGEMM_CHAIN: {
+        // the gather, hat_pos_embed, hat_norm1 and hat_attn.qkv in one kernel (AR:679-686); R (the fp32 carrier stream) is written by
+        // the kernel's first column group
+        LnGemmCall lg = {ct_ln, ha.w_qkv, L.ldn, ha.b_qkv, ct.qkv, L.ldqkv, L.ldqkv, 0};
+        FVIT_TRY(launch_ln_gemm(lg, st));
+        FVIT_TRY(run_attn(d, L, ha, AttnStart::CORE, ct, ws, st));
+        break;
+    }
+    case CarrierRoute::CHAIN:
+        FVIT_TRY(launch_gather_layernorm(ct_ln, st));
+        dbg_rowhash("ct.gather", R, L.Mc, d.C * 4, st);
+        FVIT_TRY(run_attn(d, L, ha, AttnStart::QKV_GEMM, ct, ws, st));
+        break;
+    }
+    if (r.carrier != CarrierRoute::NONE && r.carrier != CarrierRoute::FUSED_CT) FVIT_TRY(run_mlp(d, L, w.hat_mlp, r.carrier_mlp, r, ct, t, ws, st));
+
+    const FvitAttnWeights& a = w.attn;
+    switch (r.window_attn) {
+    case WinAttnRoute::WINBLK: {
+        AttnBlkCall ab = window_attnblk_call(d, L, w, t, X, R);
+        if (L.off_SLAB) {   // C = 512: heads of a window split over two sibling workgroups (fvit_tune "win_blk_split" = 2)
             ab.slab = (float*)(ws + L.off_SLAB);
             ab.counters = (int*)(ws + L.off_CNT);
-            ab.nsplit = tune_get("win_blk_split", 1);
+            ab.nsplit = r.win_blk_split;
         }
-        ab.terms = d.weight_terms;
         FVIT_TRY(launch_winblk(ab, st));
         dbg_rowhash("win.winblk", X, L.Mx, d.C * 4, st);
-    } else if (fused_attn_ok(d, w.attn, L.S, L.Mx)) {
-        // cat(ct_window(ct), x + pos_embed) gather, LN(norm1), qkv, window attention, proj, gamma3-residual -> X, one kernel
-        const float scale = (d.qk_scale > 0.f ? d.qk_scale : 1.0f / sqrtf((float)(d.C / d.heads)));
-        AttnBlkCall ab = {dt, X, rpi, R, L.G, (d.hier ? t.ln1_src : nullptr), t.ln1_add, w.pe_x, w.attn.ln_w, w.attn.ln_b, 1e-5f, rpi,
-                          w.attn.w_qkv_frag, w.attn.b_qkv_heads, w.attn.w_proj_frag, w.attn.b_proj, w.attn.gamma, w.attn.bias, X,
-                          d.batch * L.nW, L.S, d.heads, d.C, scale};
-        ab.terms = d.weight_terms;
-        FVIT_TRY(launch_attnblk(ab, st));
+        break;
+    }
+    case WinAttnRoute::ATTNBLK:
+        FVIT_TRY(launch_attnblk(window_attnblk_call(d, L, w, t, X, R), st));
         dbg_rowhash("win.attnblk", X, L.Mx, d.C * 4, st);
-    } else if (pe_preadded) {
-        // X already holds x + pos_embed (added by the previous block's fc2 epilogue): norm1 + qkv in one kernel
-        LnCall ln1 = {dt, X, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0, w.attn.ln_w, w.attn.ln_b, 1e-5f, (int)L.Mx, 1, d.C};
-        LnGemmCall lg = {ln1, w.attn.w_qkv, L.ldn, w.attn.b_qkv, QKV, L.ldqkv, L.ldqkv, 0};
+        break;
+    case WinAttnRoute::LNGEMM_PREADDED: {
+        // X already holds x + pos_embed: norm1 + qkv in one kernel
+        LnGemmCall lg = {ln_call(d, L, a.ln_w, a.ln_b, X, L.Mx, nullptr), a.w_qkv, L.ldn, a.b_qkv, win.qkv, L.ldqkv, L.ldqkv, 0};
         FVIT_TRY(launch_ln_gemm(lg, st));
-        FVIT_TRY(run_attn(d, L, w.attn, X, L.Mx, Xn, QKV, AO, d.batch * L.nW, L.S, true, st, true, ws));
-    } else {
+        FVIT_TRY(run_attn(d, L, a, AttnStart::CORE, win, ws, st));
+        break;
+    }
+    case WinAttnRoute::CHAIN: {
         // cat(ct_window(ct), x + pos_embed) gather -> X, LN(norm1) -> Xn
-        const int AT = d.weight_terms == 3 ? 2 : 1;
-        LnCall ln1 = {dt, X, rpi, R, L.G, (d.hier ? t.ln1_src : nullptr), t.ln1_add, w.pe_x, X, Xn, AT * L.ldn,
-                      w.attn.ln_w, w.attn.ln_b, 1e-5f, (int)L.Mx, rpi, d.C};
-        if (AT == 2) ln1.lo_off = L.ldn;
+        LnCall ln1 = ln_call(d, L, a.ln_w, a.ln_b, X, L.Mx, win.xn);
+        ln1.rowsA = L.rpi; ln1.srcB = R; ln1.rowsB = L.G; ln1.src_idx = d.hier ? t.ln1_src : nullptr; ln1.add_idx = t.ln1_add; ln1.add = w.pe_x;
+        ln1.x_out = X; ln1.rows_per_image = L.rpi;
         FVIT_TRY(launch_gather_layernorm(ln1, st));
         dbg_rowhash("win.gather", X, L.Mx, d.C * 4, st);
-        FVIT_TRY(run_attn(d, L, w.attn, X, L.Mx, Xn, QKV, AO, d.batch * L.nW, L.S, true, st, false, ws));
+        FVIT_TRY(run_attn(d, L, a, AttnStart::QKV_GEMM, win, ws, st));
+        break;
     }
-    FVIT_TRY(run_mlp(d, L, w.mlp, X, L.Mx, Xn, Hb, st, next_pe, ws));
-    return FVIT_OK;
+    }
+    return run_mlp(d, L, w.mlp, r.window_mlp, r, win, t, ws, st);
 }
 
-static bool check_tables(const FvitStageDesc& d, const FvitStageTables* t) {
+// What the stage and the block entry check before the first launch; `carrier` is the entry's carrier-token argument
+static int check_hat_call(const FvitStageDesc* desc, bool args_ok, const FvitStageTables* t, const void* workspace, size_t workspace_bytes,
+                          const void* carrier, const char* no_carrier, StageLayout& L) {
+    if (!desc || !args_ok) {
+        set_error("null argument");
+        return FVIT_EINVAL;
+    }
+    const FvitStageDesc& d = *desc;
+    if (!make_layout(d, L)) return FVIT_EINVAL;
     if (!t || !t->ln1_add || (d.hier && (!t->ln1_src || !t->ct_src)) || (d.hier && d.do_propagation && !t->up_idx)) {
         set_error("stage tables missing (ln1_add%s)", d.hier ? ", ln1_src, ct_src, up_idx" : "");
-        return false;
+        return FVIT_EINVAL;
     }
-    return true;
+    if (!workspace || workspace_bytes < L.total) {
+        set_error("workspace too small: %zu < %zu", workspace_bytes, L.total);
+        return FVIT_EWORKSPACE;
+    }
+    if (d.hier && !carrier) {
+        set_error("%s", no_carrier);
+        return FVIT_EINVAL;
+    }
+    return FVIT_OK;
 }
 
 }  // namespace fvit
@@ -483,20 +602,8 @@ int fvit_hat_stage_forward(const FvitStageDesc* desc, const FvitBlockWeights* bl
                            const FvitMapView* in, const float* ct_init, const FvitMapView* out, void* workspace,
                            size_t workspace_bytes, fvit_stream_t stream) {
     StageLayout L;
-    if (!desc || !blocks || !in || !out || !make_layout(*desc, L)) {
-        if (!desc || !blocks || !in || !out) set_error("null argument");
-        return FVIT_EINVAL;
-    }
+    FVIT_TRY(check_hat_call(desc, blocks && in && out, tables, workspace, workspace_bytes, ct_init, "hierarchical stage needs ct_init", L));
     const FvitStageDesc& d = *desc;
-    if (!check_tables(d, tables)) return FVIT_EINVAL;
-    if (!workspace || workspace_bytes < L.total) {
-        set_error("workspace too small: %zu < %zu", workspace_bytes, L.total);
-        return FVIT_EWORKSPACE;
-    }
-    if (d.hier && !ct_init) {
-        set_error("hierarchical stage needs ct_init");
-        return FVIT_EINVAL;
-    }
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     float* X = (float*)(ws + L.off_X);
@@ -505,14 +612,16 @@ int fvit_hat_stage_forward(const FvitStageDesc* desc, const FvitBlockWeights* bl
     dbg_rowhash("partition", X, L.Mx, d.C * 4, st);
     // (r03-r05 carried an opt-in ONE-launch form of a non-hierarchical C = 512 stage -- persistent per-window workgroups running the two kernel bodies alternately,
     // fvit_stage3.hip: measured -3 % in the joined launch structure, removed in r06: git history, profiles/HISTORY.md)
-    bool pre = false;   // does X already include block i's position embedding?
-    for (int i = 0; i < d.depth; ++i) {
-        NextPe np;
-        const bool chain = i + 1 < d.depth && pe_preadd_chain(d, L, blocks[i]) && pe_preadd_chain(d, L, blocks[i + 1]) && blocks[i + 1].pe_x;
-        if (chain) { np.add = blocks[i + 1].pe_x; np.add_idx = tables->ln1_add; np.rows_per_image = L.nW * L.S; }
-        FVIT_TRY(run_block(d, L, blocks[i], *tables, ws, st, pre, chain ? &np : nullptr));
-        pre = chain;
+    const RouteKnobs knobs{};
+    std::vector<BlockRoute> routes;
+    for (int i = 0; i < d.depth; ++i) routes.push_back(choose_route(d, L, blocks[i], knobs));
+    for (int i = 0; i + 1 < d.depth; ++i) {   // the position-embedding pre-add chain (BlockRoute)
+        if (routes[i].preadd_eligible && routes[i + 1].preadd_eligible && blocks[i + 1].pe_x) {
+            routes[i].pe_next = blocks[i + 1].pe_x;
+            routes[i + 1].window_attn = WinAttnRoute::LNGEMM_PREADDED;
+        }
     }
+    for (int i = 0; i < d.depth; ++i) FVIT_TRY(run_block(d, L, routes[i], blocks[i], *tables, ws, st));
     const bool prop = d.hier && d.do_propagation && d.depth > 0 && blocks[d.depth - 1].last;
     ReverseCall rc = {X, L.S, L.ncw, d.batch, d.C, d.Hp, d.Wp, d.H, d.W, d.ws, *out,
                       prop ? blocks[d.depth - 1].hat_attn.gamma : nullptr, prop ? tables->up_idx : nullptr};
@@ -523,27 +632,15 @@ int fvit_hat_stage_forward(const FvitStageDesc* desc, const FvitBlockWeights* bl
 int fvit_hat_block_forward(const FvitStageDesc* desc, const FvitBlockWeights* block, const FvitStageTables* tables, float* x,
                            float* ct, void* workspace, size_t workspace_bytes, fvit_stream_t stream) {
     StageLayout L;
-    if (!desc || !block || !x || !make_layout(*desc, L)) {
-        if (!desc || !block || !x) set_error("null argument");
-        return FVIT_EINVAL;
-    }
+    FVIT_TRY(check_hat_call(desc, block && x, tables, workspace, workspace_bytes, ct, "hierarchical block needs carrier tokens", L));
     const FvitStageDesc& d = *desc;
-    if (!check_tables(d, tables)) return FVIT_EINVAL;
-    if (!workspace || workspace_bytes < L.total) {
-        set_error("workspace too small: %zu < %zu", workspace_bytes, L.total);
-        return FVIT_EWORKSPACE;
-    }
-    if (d.hier && !ct) {
-        set_error("hierarchical block needs carrier tokens");
-        return FVIT_EINVAL;
-    }
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     float* X = (float*)(ws + L.off_X);
     const int nwin = d.batch * L.nW;
     FVIT_TRY(launch_ct_copy(X, L.S, L.ncw, L.nloc, x, nwin, d.C, 1, st));
     if (d.hier) FVIT_TRY(launch_ct_copy(X, L.S, 0, L.ncw, ct, nwin, d.C, 1, st));
-    FVIT_TRY(run_block(d, L, *block, *tables, ws, st));
+    FVIT_TRY(run_block(d, L, choose_route(d, L, *block, RouteKnobs{}), *block, *tables, ws, st));
     if (d.hier && block->last && d.do_propagation)
         FVIT_TRY(launch_propagate(X, block->hat_attn.gamma, tables->up_idx, L.S, L.ncw, L.nloc, nwin, d.C, st));
     FVIT_TRY(launch_ct_copy(X, L.S, L.ncw, L.nloc, x, nwin, d.C, 0, st));
@@ -694,8 +791,8 @@ int fvit_attn_block_fused(int32_t operand_dtype, const float* srcA, int32_t rows
                           int32_t rows_per_image, const void* w_qkv_frag, const float* b_qkv_heads, const void* w_proj_frag,
                           const float* b_proj, const float* gamma, const float* bias, float* x_out, int32_t nwin, int32_t S,
                           int32_t heads, int32_t C, float scale, fvit_stream_t stream) {
-    AttnBlkCall ab = {operand_dtype, srcA, rowsA, srcB, rowsB, src_idx, add_idx, add, ln_w, ln_b, eps, rows_per_image, w_qkv_frag,
-                      b_qkv_heads, w_proj_frag, b_proj, gamma, bias, x_out, nwin, S, heads, C, scale};
+    AttnBlkCall ab = attnblk_call(operand_dtype, srcA, rowsA, srcB, rowsB, src_idx, add_idx, add, ln_w, ln_b, eps, rows_per_image, w_qkv_frag,
+                                  b_qkv_heads, w_proj_frag, b_proj, gamma, bias, x_out, nwin, S, heads, C, scale);
     return launch_attnblk(ab, (hipStream_t)stream);
 }
 
@@ -706,8 +803,8 @@ int fvit_debug_attn_block_timeline(const float* srcA, int32_t rowsA, const float
                                    const float* b_proj, const float* gamma, const float* bias, float* x_out, int32_t nwin, int32_t S,
                                    int32_t heads, int32_t C, float scale, void* stamps, fvit_stream_t stream) {
     if (!stamps) { set_error("debug_attn_block_timeline: null stamp buffer"); return FVIT_EINVAL; }
-    AttnBlkCall ab = {FVIT_F16, srcA, rowsA, srcB, rowsB, src_idx, add_idx, add, ln_w, ln_b, eps, rows_per_image, w_qkv_frag,
-                      b_qkv_heads, w_proj_frag, b_proj, gamma, bias, x_out, nwin, S, heads, C, scale};
+    AttnBlkCall ab = attnblk_call(FVIT_F16, srcA, rowsA, srcB, rowsB, src_idx, add_idx, add, ln_w, ln_b, eps, rows_per_image, w_qkv_frag,
+                                  b_qkv_heads, w_proj_frag, b_proj, gamma, bias, x_out, nwin, S, heads, C, scale);
     ab.ts = stamps;
     return launch_attnblk(ab, (hipStream_t)stream);
 }
@@ -718,14 +815,15 @@ int fvit_win_mlp_supported(int32_t C, int32_t hidden) { return winmlp_supported(
 int fvit_win_mlp_fused(int32_t operand_dtype, float* x, int32_t M, int32_t C, int32_t hidden, const float* ln_w, const float* ln_b,
                        float eps, const void* w_fc1_frag, const float* b_fc1, const void* w_fc2_frag, const float* b_fc2,
                        const float* gamma, fvit_stream_t stream) {
-    MlpFusedCall mc = {operand_dtype, x, M, C, hidden, ln_w, ln_b, eps, w_fc1_frag, b_fc1, w_fc2_frag, b_fc2, gamma};
+    MlpFusedCall mc = mlp_fused_call(operand_dtype, x, M, C, hidden, ln_w, ln_b, eps, w_fc1_frag, b_fc1, w_fc2_frag, b_fc2, gamma);
     return launch_winmlp(mc, (hipStream_t)stream);
 }
 
 int fvit_win_mlp_fused_terms(int32_t operand_dtype, float* x, int32_t M, int32_t C, int32_t hidden, const float* ln_w, const float* ln_b,
                              float eps, const void* w_fc1_frag, const float* b_fc1, const void* w_fc2_frag, const float* b_fc2,
                              const float* gamma, int32_t terms, fvit_stream_t stream) {
-    MlpFusedCall mc = {operand_dtype, x, M, C, hidden, ln_w, ln_b, eps, w_fc1_frag, b_fc1, w_fc2_frag, b_fc2, gamma, terms};
+    MlpFusedCall mc = mlp_fused_call(operand_dtype, x, M, C, hidden, ln_w, ln_b, eps, w_fc1_frag, b_fc1, w_fc2_frag, b_fc2, gamma);
+    mc.terms = terms;
     return launch_winmlp(mc, (hipStream_t)stream);
 }
 
@@ -738,7 +836,8 @@ int fvit_win_mlp_fused_split(int32_t operand_dtype, float* x, int32_t M, int32_t
         set_error("win_mlp_fused_split: C = %d nsplit = %d (C must be 512, nsplit 1 / 2 with scratch)", C, nsplit);
         return FVIT_EINVAL;
     }
-    MlpFusedCall mc = {operand_dtype, x, M, C, hidden, ln_w, ln_b, eps, w_fc1_frag, b_fc1, w_fc2_frag, b_fc2, gamma, terms};
+    MlpFusedCall mc = mlp_fused_call(operand_dtype, x, M, C, hidden, ln_w, ln_b, eps, w_fc1_frag, b_fc1, w_fc2_frag, b_fc2, gamma);
+    mc.terms = terms;
     mc.slab = slab; mc.counters = counters; mc.nsplit = nsplit;
     return launch_winmlp(mc, (hipStream_t)stream);
 }
@@ -750,8 +849,8 @@ int fvit_win_block_fused(int32_t operand_dtype, const float* srcA, int32_t rowsA
                          int32_t rows_per_image, const void* w_qkv_frag, const float* b_qkv_heads, const void* w_proj_frag,
                          const float* b_proj, const float* gamma, const float* bias, float* x_out, int32_t nwin, int32_t S,
                          int32_t heads, int32_t C, float scale, fvit_stream_t stream) {
-    AttnBlkCall ab = {operand_dtype, srcA, rowsA, srcB, rowsB, src_idx, add_idx, add, ln_w, ln_b, eps, rows_per_image, w_qkv_frag,
-                      b_qkv_heads, w_proj_frag, b_proj, gamma, bias, x_out, nwin, S, heads, C, scale};
+    AttnBlkCall ab = attnblk_call(operand_dtype, srcA, rowsA, srcB, rowsB, src_idx, add_idx, add, ln_w, ln_b, eps, rows_per_image, w_qkv_frag,
+                                  b_qkv_heads, w_proj_frag, b_proj, gamma, bias, x_out, nwin, S, heads, C, scale);
     return launch_winblk(ab, (hipStream_t)stream);
 }
 
@@ -760,7 +859,7 @@ int fvit_debug_win_mlp_timeline(float* x, int32_t M, int32_t C, int32_t hidden, 
                                 const void* w_fc1_frag, const float* b_fc1, const void* w_fc2_frag, const float* b_fc2, const float* gamma,
                                 void* stamps, fvit_stream_t stream) {
     if (!stamps) { set_error("debug_win_mlp_timeline: null stamp buffer"); return FVIT_EINVAL; }
-    MlpFusedCall mc = {FVIT_F16, x, M, C, hidden, ln_w, ln_b, eps, w_fc1_frag, b_fc1, w_fc2_frag, b_fc2, gamma, 1};
+    MlpFusedCall mc = mlp_fused_call(FVIT_F16, x, M, C, hidden, ln_w, ln_b, eps, w_fc1_frag, b_fc1, w_fc2_frag, b_fc2, gamma);
     mc.ts = stamps;
     return launch_winmlp(mc, (hipStream_t)stream);
 }
@@ -775,8 +874,8 @@ int fvit_win_block_fused_split(int32_t operand_dtype, const float* srcA, int32_t
         set_error("win_block_fused_split: C = %d nsplit = %d (C must be 512, nsplit 1 / 2 with scratch)", C, nsplit);
         return FVIT_EINVAL;
     }
-    AttnBlkCall ab = {operand_dtype, srcA, rowsA, srcB, rowsB, src_idx, add_idx, add, ln_w, ln_b, eps, rows_per_image, w_qkv_frag,
-                      b_qkv_heads, w_proj_frag, b_proj, gamma, bias, x_out, nwin, S, heads, C, scale};
+    AttnBlkCall ab = attnblk_call(operand_dtype, srcA, rowsA, srcB, rowsB, src_idx, add_idx, add, ln_w, ln_b, eps, rows_per_image, w_qkv_frag,
+                                  b_qkv_heads, w_proj_frag, b_proj, gamma, bias, x_out, nwin, S, heads, C, scale);
     ab.slab = slab; ab.counters = counters; ab.nsplit = nsplit;
     return launch_winblk(ab, (hipStream_t)stream);
 }
@@ -786,8 +885,8 @@ int fvit_win_block_fused_terms(int32_t operand_dtype, const float* srcA, int32_t
                                int32_t rows_per_image, const void* w_qkv_frag, const float* b_qkv_heads, const void* w_proj_frag,
                                const float* b_proj, const float* gamma, const float* bias, float* x_out, int32_t nwin, int32_t S,
                                int32_t heads, int32_t C, float scale, int32_t terms, fvit_stream_t stream) {
-    AttnBlkCall ab = {operand_dtype, srcA, rowsA, srcB, rowsB, src_idx, add_idx, add, ln_w, ln_b, eps, rows_per_image, w_qkv_frag,
-                      b_qkv_heads, w_proj_frag, b_proj, gamma, bias, x_out, nwin, S, heads, C, scale};
+    AttnBlkCall ab = attnblk_call(operand_dtype, srcA, rowsA, srcB, rowsB, src_idx, add_idx, add, ln_w, ln_b, eps, rows_per_image, w_qkv_frag,
+                                  b_qkv_heads, w_proj_frag, b_proj, gamma, bias, x_out, nwin, S, heads, C, scale);
     ab.terms = terms;
     return launch_winblk(ab, (hipStream_t)stream);
 }
@@ -797,8 +896,8 @@ int fvit_attn_block_fused_terms(int32_t operand_dtype, const float* srcA, int32_
                                 int32_t rows_per_image, const void* w_qkv_frag, const float* b_qkv_heads, const void* w_proj_frag,
                                 const float* b_proj, const float* gamma, const float* bias, float* x_out, int32_t nwin, int32_t S,
                                 int32_t heads, int32_t C, float scale, int32_t terms, fvit_stream_t stream) {
-    AttnBlkCall ab = {operand_dtype, srcA, rowsA, srcB, rowsB, src_idx, add_idx, add, ln_w, ln_b, eps, rows_per_image, w_qkv_frag,
-                      b_qkv_heads, w_proj_frag, b_proj, gamma, bias, x_out, nwin, S, heads, C, scale};
+    AttnBlkCall ab = attnblk_call(operand_dtype, srcA, rowsA, srcB, rowsB, src_idx, add_idx, add, ln_w, ln_b, eps, rows_per_image, w_qkv_frag,
+                                  b_qkv_heads, w_proj_frag, b_proj, gamma, bias, x_out, nwin, S, heads, C, scale);
     ab.terms = terms;
     return launch_attnblk(ab, (hipStream_t)stream);
 }
@@ -810,8 +909,8 @@ int fvit_ct_block_fused(int32_t operand_dtype, const float* X, int32_t rowsA, co
                         const void* w_qkv_frag, const float* b_qkv_heads, const void* w_proj_frag, const float* b_proj, const float* gamma1,
                         const float* bias, float scale, const float* ln2_w, const float* ln2_b, const void* w_fc1_frag, const float* b_fc1,
                         const void* w_fc2_frag, const float* b_fc2, const float* gamma2, float eps, fvit_stream_t stream) {
-    CtBlkCall cb = {operand_dtype, X, rowsA, src_idx, add, R, batch, G, heads, C, hidden, ln1_w, ln1_b, w_qkv_frag, b_qkv_heads, w_proj_frag,
-                    b_proj, gamma1, bias, scale, ln2_w, ln2_b, w_fc1_frag, b_fc1, w_fc2_frag, b_fc2, gamma2, eps};
+    CtBlkCall cb = ctblk_call(operand_dtype, X, rowsA, src_idx, add, R, batch, G, heads, C, hidden, ln1_w, ln1_b, w_qkv_frag, b_qkv_heads, w_proj_frag,
+                              b_proj, gamma1, bias, scale, ln2_w, ln2_b, w_fc1_frag, b_fc1, w_fc2_frag, b_fc2, gamma2, eps);
     return launch_ctblk(cb, (hipStream_t)stream);
 }
 
@@ -820,8 +919,9 @@ int fvit_ct_block_fused_terms(int32_t operand_dtype, const float* X, int32_t row
                               const void* w_qkv_frag, const float* b_qkv_heads, const void* w_proj_frag, const float* b_proj, const float* gamma1,
                               const float* bias, float scale, const float* ln2_w, const float* ln2_b, const void* w_fc1_frag, const float* b_fc1,
                               const void* w_fc2_frag, const float* b_fc2, const float* gamma2, float eps, int32_t terms, fvit_stream_t stream) {
-    CtBlkCall cb = {operand_dtype, X, rowsA, src_idx, add, R, batch, G, heads, C, hidden, ln1_w, ln1_b, w_qkv_frag, b_qkv_heads, w_proj_frag,
-                    b_proj, gamma1, bias, scale, ln2_w, ln2_b, w_fc1_frag, b_fc1, w_fc2_frag, b_fc2, gamma2, eps, terms};
+    CtBlkCall cb = ctblk_call(operand_dtype, X, rowsA, src_idx, add, R, batch, G, heads, C, hidden, ln1_w, ln1_b, w_qkv_frag, b_qkv_heads, w_proj_frag,
+                              b_proj, gamma1, bias, scale, ln2_w, ln2_b, w_fc1_frag, b_fc1, w_fc2_frag, b_fc2, gamma2, eps);
+    cb.terms = terms;
     return launch_ctblk(cb, (hipStream_t)stream);
 }
 
@@ -832,8 +932,8 @@ int fvit_debug_ct_block_timeline(const float* X, int32_t rowsA, const int32_t* s
                                  const float* bias, float scale, const float* ln2_w, const float* ln2_b, const void* w_fc1_frag, const float* b_fc1,
                                  const void* w_fc2_frag, const float* b_fc2, const float* gamma2, float eps, void* stamps, fvit_stream_t stream) {
     if (!stamps) { set_error("debug_ct_block_timeline: null stamp buffer"); return FVIT_EINVAL; }
-    CtBlkCall cb = {FVIT_F16, X, rowsA, src_idx, add, R, batch, G, heads, C, hidden, ln1_w, ln1_b, w_qkv_frag, b_qkv_heads, w_proj_frag,
-                    b_proj, gamma1, bias, scale, ln2_w, ln2_b, w_fc1_frag, b_fc1, w_fc2_frag, b_fc2, gamma2, eps, 1};
+    CtBlkCall cb = ctblk_call(FVIT_F16, X, rowsA, src_idx, add, R, batch, G, heads, C, hidden, ln1_w, ln1_b, w_qkv_frag, b_qkv_heads, w_proj_frag,
+                              b_proj, gamma1, bias, scale, ln2_w, ln2_b, w_fc1_frag, b_fc1, w_fc2_frag, b_fc2, gamma2, eps);
     cb.ts = stamps;
     return launch_ctblk(cb, (hipStream_t)stream);
 }
@@ -844,7 +944,7 @@ int fvit_mlp_fused_supported(int32_t C, int32_t hidden) { return mlp_fused_suppo
 int fvit_mlp_fused(int32_t operand_dtype, float* x, int32_t M, int32_t C, int32_t hidden, const float* ln_w, const float* ln_b,
                    float eps, const void* w_fc1_frag, const float* b_fc1, const void* w_fc2_frag, const float* b_fc2,
                    const float* gamma, fvit_stream_t stream) {
-    MlpFusedCall mc = {operand_dtype, x, M, C, hidden, ln_w, ln_b, eps, w_fc1_frag, b_fc1, w_fc2_frag, b_fc2, gamma};
+    MlpFusedCall mc = mlp_fused_call(operand_dtype, x, M, C, hidden, ln_w, ln_b, eps, w_fc1_frag, b_fc1, w_fc2_frag, b_fc2, gamma);
     return launch_mlp_fused(mc, (hipStream_t)stream);
 }
 
