@@ -35,6 +35,7 @@ measured 6.5e-4 .. 9.5e-4 max-abs on FasterViT-0 (asserted < 1e-3 in tests/test_
 """
 from __future__ import annotations
 
+import ctypes
 import os
 from typing import NamedTuple, Optional
 
@@ -283,6 +284,12 @@ class DeployPlan:
                                   self._padv(ds.norm.bias.float(), self._cp(cin)).contiguous(), float(ds.norm.eps),
                                   self._cw(ds.reduction[0].weight.float(), terms=2 if (self.down_weight_terms == 2 or ct == 2) else 1), cin)
             t["levels"].append(e)
+        self._build_head(t)
+        self.t = t
+
+    def _build_head(self, t):
+        """``t["head"]``: final norm + pool + head as one fp32 Linear (+ the LayerNorm2d parameters with layer_norm_last)."""
+        m = self.model
         if isinstance(m.head, torch.nn.Linear):
             hw = m.head.weight.float()
             hb = m.head.bias.float() if m.head.bias is not None else torch.zeros(hw.shape[0], device=hw.device)
@@ -295,7 +302,6 @@ class DeployPlan:
         else:  # layer_norm_last: LayerNorm2d kernel, then pool + head
             t["head"] = HeadW(hw.contiguous(), hb.contiguous(),
                               (m.norm.weight.float().contiguous(), m.norm.bias.float().contiguous(), float(m.norm.eps)))
-        self.t = t
 
     # ---- kernels -------------------------------------------------------------------------
     def _bias_act(self, x, bias, act):
@@ -545,8 +551,9 @@ class DeployPlan:
             hi, lo = self._conv_px(y, None, b.conv2, b.bias2, 1, 0, res=hi, res_lo=lo)         # conv2 + BN (+ gamma) + residual, in place on the stream
         return hi, lo, None
 
-    def _hat_level(self, lvl, x, padded_out):
-        """A transformer level (``hat_runtime.stage_forward``) on a 16-bit map, or -- precise plan -- from and to an fp32 map."""
+    def _hat_level(self, lvl, x, padded_out, tokenizer=None):
+        """A transformer level (``hat_runtime.stage_forward``) on a 16-bit map, or -- precise plan -- from and to an fp32 map.  ``tokenizer``: passed on
+        (the detection backbone's per-call TokenInitializer)."""
         if self.precise:
             hi, lo, x = x
             if x is None:   # a transformer level behind a conv level without a Downsample in between (no reference entrypoint does this)
@@ -562,9 +569,9 @@ class DeployPlan:
                          memory_format=torch.channels_last)
         if cpo != creal:
             xo[:, creal:] = 0   # only the pad channels need initialising; the stage writes the first creal
-            hat_runtime.stage_forward(lvl, xin, out=xo[:, :creal])  # TokenInitializer: fvit_token_init in both modes
+            hat_runtime.stage_forward(lvl, xin, tokenizer=tokenizer, out=xo[:, :creal])  # TokenInitializer: fvit_token_init in both modes
         else:
-            xo = hat_runtime.stage_forward(lvl, xin, out=xo)
+            xo = hat_runtime.stage_forward(lvl, xin, tokenizer=tokenizer, out=xo)
         return (None, None, xo) if self.precise else xo
 
     def _downsample(self, x, d: DownW, f32_out):
@@ -591,6 +598,146 @@ class DeployPlan:
             nh, nl = self._ln2d_px(None, None, f32.contiguous(memory_format=torch.channels_last), *ln, f32.shape[1])
             f32 = nh.float() + nl.float()
         return self._pool_head(f32, hw, hb)
+
+
+class LevelMap(NamedTuple):
+    """The map ``BackboneDeployPlan`` hands from level to level: a 16-bit channels_last tensor (channels padded to ``_cp``) whose top-left H x W
+    pixels are the level's map.  Behind a padded conv level the tensor is the whole window-padded Hp x Wp map (the ConvBlocks' values in the pad,
+    which only they read); everywhere else it is dense (``x.shape[2:] == (H, W)``)."""
+    x: torch.Tensor
+    H: int
+    W: int
+
+    @property
+    def dense(self) -> bool:
+        return self.x.shape[2] == self.H and self.x.shape[3] == self.W
+
+
+TapW = NamedTuple("TapW", [("scale", torch.Tensor), ("shift", torch.Tensor), ("channels", int)])   # t["taps"][i]: norm{i} folded (fp32), real channels of level i
+
+
+class BackboneDeployPlan(DeployPlan):
+    """The deploy plan of ``models.backbone.FasterViTBackbone``: ``DeployPlan``'s folded weights, conv / LayerNorm2d / stem launches
+    and transformer-level call, under the detection variant's level walk -- every level window-padded and cropped (DET:687-704), the ``out_indices``
+    levels' pre-downsample maps returned through ``fvit_feature_tap`` with ``norm{i}`` folded.  Per level:
+
+      conv level         H x W not a window multiple: ``fvit_map_pad_cl`` copies the dense map into a zero-padded Hp x Wp one (one pass), the ConvBlocks
+                         run on it in place (the second conv of a block reads the first one's values in the pad, as the reference does); the tap reads
+                         the H x W corner through strides and the Downsample's LayerNorm2d reads it through ``fvit_layernorm2d_crop_cl``, so the crop
+                         costs no pass.  A window multiple: the classifier's path.
+      transformer level  ``hat_runtime.stage_forward`` on the 16-bit map with the per-call tokenizer (it pads and crops itself), the tap, then the dense
+                         LayerNorm2d + strided conv.
+
+    ``forward`` returns the tuple of NCHW fp32 maps of ``FasterViTBackbone.forward_features``.  16-bit plan only: the precise plan, two-term conv
+    weights and stream shards are refused by name."""
+
+    def __init__(self, model, dtype=torch.float16):
+        super().__init__(model, dtype)
+        self._check_options()
+        for i in model.out_indices:   # a norm{i} without running statistics: refused here, with feature_tap's message
+            bn = getattr(model, f"norm{i}")
+            hat_runtime._folded_bn(bn, (bn.running_mean if bn.running_mean is not None else next(model.parameters())).device)
+
+    def _check_options(self):
+        if self.precise:
+            raise NotImplementedError("backbone deploy plan: precise=True is not implemented (there is no two-term feature tap); use the 16-bit plan, "
+                                      "or module mode with set_hat_operand_dtype('f16x3')")
+        if self.conv_weight_terms != 1 or self.down_weight_terms != 1:
+            raise NotImplementedError("backbone deploy plan: two-term conv weights (conv_weight_terms / down_weight_terms = 2) are not implemented")
+        if self.streams != 1:
+            raise NotImplementedError("backbone deploy plan: streams > 1 (stream shards) is not implemented; detection batches are small")
+
+    def _build_head(self, t):
+        """No head: ``t["taps"]`` = the ``out_indices`` levels' ``norm{i}`` folded to scale / shift (``hat_runtime._folded_bn``).  Their tensors are part of
+        ``_signature`` (every parameter and buffer outside the HAT blocks), so a change rebuilds them with the conv weights."""
+        m = self.model
+        dev = next(m.parameters()).device
+        t["taps"] = {i: TapW(*hat_runtime._folded_bn(getattr(m, f"norm{i}"), dev), m.num_features[i]) for i in m.out_indices}
+
+    # ---- forward -------------------------------------------------------------------------
+    def forward(self, x):
+        self._check_options()
+        self._enter(x)
+        with torch.cuda.device(x.device):
+            self._refresh()
+            with hat_runtime.workspace_slot(self.slot_base):
+                return self._walk(x)
+
+    forward_single = forward
+
+    def _walk(self, x):
+        """Stem, then per level: blocks -> tap (``out_indices``) -> Downsample.  ``m`` is the ``LevelMap`` between the steps."""
+        levels, taps = self.model.levels, self.t["taps"]
+        outs = []
+        with torch.autocast(device_type="cuda", enabled=False):
+            y = self._stem(x)
+            m = LevelMap(y, y.shape[2], y.shape[3])
+            for li, (lvl, e) in enumerate(zip(levels, self.t["levels"])):
+                if "blocks" in e:
+                    m = self._conv_level_padded(m, e["blocks"], lvl.window_size)
+                else:
+                    m = self._hat_level_dyn(lvl, m, padded_out="down" in e)
+                if li in taps:
+                    outs.append(self._tap(m, taps[li]))
+                if "down" in e:
+                    m = self._downsample_crop(m, e["down"])
+        return tuple(outs)
+
+    def _conv_level_padded(self, m: LevelMap, blocks, ws: int) -> LevelMap:
+        """The ConvBlocks on the window-padded map (DET:687-704), in place; the result keeps the pad around the H x W map."""
+        assert m.dense
+        B, C, H, W = m.x.shape
+        Hp, Wp = H + (ws - H % ws) % ws, W + (ws - W % ws) % ws
+        x = m.x
+        if (Hp, Wp) != (H, W) and len(blocks):
+            x = torch.empty((B, C, Hp, Wp), dtype=self.dtype, device=m.x.device, memory_format=torch.channels_last)
+            _lib.check(_lib.lib().fvit_map_pad_cl(self.code, m.x.data_ptr(), x.data_ptr(), B, H, W, Hp, Wp, C, _stream(self.dev)), "fvit_map_pad_cl")
+        return LevelMap(self._conv_level(x, blocks), H, W)
+
+    def _hat_level_dyn(self, lvl, m: LevelMap, padded_out: bool) -> LevelMap:
+        """A transformer level with the window grid and TokenInitializer pooling of THIS map size; dense in, dense out."""
+        assert m.dense
+        tok = None
+        if len(lvl.blocks) and lvl.do_gt and lvl.blocks[0].do_sr_hat:
+            tok = lambda xp: hat_runtime.token_init_dyn(lvl.global_tokenizer, xp, lvl.window_size)   # noqa: E731
+        return LevelMap(self._hat_level(lvl, m.x, padded_out, tokenizer=tok), m.H, m.W)
+
+    def _tap(self, m: LevelMap, tw: TapW) -> torch.Tensor:
+        """``norm{i}`` of the H x W corner's real channels -> contiguous NCHW fp32 (fvit_feature_tap reads the crop through strides)."""
+        B = m.x.shape[0]
+        view = hat_runtime._map_view(m.x[:, :tw.channels, :m.H, :m.W])
+        out = torch.empty((B, tw.channels, m.H, m.W), dtype=torch.float32, device=m.x.device)
+        _lib.check(_lib.lib().fvit_feature_tap(ctypes.byref(view), B, tw.channels, m.H, m.W, tw.scale.data_ptr(), tw.shift.data_ptr(), out.data_ptr(),
+                                               _stream(self.dev)), "fvit_feature_tap")
+        return out
+
+    def _downsample_crop(self, m: LevelMap, d: DownW) -> LevelMap:
+        """Downsample of the H x W corner: LayerNorm2d (``fvit_layernorm2d_crop_cl`` on a padded map: the crop costs no pass) + strided conv."""
+        if m.dense:
+            n = self._ln2d(m.x, d.ln_w, d.ln_b, d.eps, d.cin)
+        else:
+            B, C, Hp, Wp = m.x.shape
+            n = torch.empty((B, C, m.H, m.W), dtype=self.dtype, device=m.x.device, memory_format=torch.channels_last)
+            _lib.check(_lib.lib().fvit_layernorm2d_crop_cl(self.code, m.x.data_ptr(), n.data_ptr(), d.ln_w.data_ptr(), d.ln_b.data_ptr(), d.eps,
+                                                           B, m.H, m.W, Hp, Wp, C, d.cin, _stream(self.dev)), "fvit_layernorm2d_crop_cl")
+        y = self._conv(n, d.conv, None, 2, 0)
+        return LevelMap(y, y.shape[2], y.shape[3])
+
+    # ---- what a captured graph holds by raw pointer ------------------------------------------
+    def pinned(self, x_shape, device):
+        """Strong references to the per-geometry objects of ``hat_runtime`` (packed weights, tables, workspace of this plan's slot, tokenizer
+        weights) that a forward of an input of ``x_shape`` uses, after such a forward has run: ``hat_runtime`` keeps them in a bounded LRU, a captured
+        graph holds their addresses.  (The plan owns the folded conv weights, taps and the zero page itself.)"""
+        B, _, H, W = x_shape
+        for _ in range(2):   # the stem's two stride-2 convs; each Downsample: one more
+            H, W = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        refs = []
+        for lvl in self.model.levels:
+            if lvl.transformer_block and len(lvl.blocks):
+                refs.append(hat_runtime.stage_refs(lvl, device, B, H, W, self.slot_base))
+            if lvl.downsample is not None:
+                H, W = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        return refs
 
 
 class ShardRunner:

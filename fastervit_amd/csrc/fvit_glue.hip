@@ -53,19 +53,28 @@ __global__ __launch_bounds__(256) void bias_kernel(T* __restrict__ x, const T* _
 // LPP lanes cooperate on one pixel (64 / LPP pixels per wave); the pixel's C channels live in registers,
 // 8 per lane and per step (MAXV steps).  LPP = 8 for C = 64 so that narrow maps still use every lane.
 // PX (fvit_layernorm2d_px): the input is a two-term map (in + in_lo, 16-bit planes) or ONE fp32 map (in_f32), the output two planes out / out_lo
-template <typename T, int LPP, int MAXV, bool PX = false>
+// CROP (fvit_layernorm2d_crop_cl): the input is the H x W corner of a padded [B][Hp][Wp][C] map, the output the dense [B][H][W][C] map.  blockIdx.y is
+// the image and npix = H * W its pixels, so the only extra arithmetic is one 32-bit division per lane; everything behind the source address is the
+// dense kernel's body (same loads per lane group, same sums in the same order: the same bits per pixel).
+template <typename T, int LPP, int MAXV, bool PX = false, bool CROP = false>
 __global__ __launch_bounds__(256) void ln2d_kernel(const T* __restrict__ in, T* __restrict__ out, const float* __restrict__ w,
                                                    const float* __restrict__ b, float eps, int64_t npix, int C, int Cv,
                                                    const T* __restrict__ in_lo = nullptr, const float* __restrict__ in_f32 = nullptr,
-                                                   T* __restrict__ out_lo = nullptr) {
+                                                   T* __restrict__ out_lo = nullptr, int W = 0, int Hp = 0, int Wp = 0) {
     typedef T v8 __attribute__((ext_vector_type(8)));
     constexpr int PPW = 64 / LPP;  // pixels per wave
     const int lane = threadIdx.x & 63;
     const int sub = lane % LPP;
-    const int64_t pix = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * PPW + lane / LPP;
+    int64_t pix = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * PPW + lane / LPP;
     const bool ok = pix < npix;
+    int64_t spix = ok ? pix : 0;   // pixel index in the source map
+    if (CROP) {
+        const unsigned p = (unsigned)spix, y = p / (unsigned)W, x = p - y * (unsigned)W;
+        spix = ((int64_t)blockIdx.y * Hp + y) * Wp + x;
+        pix += (int64_t)blockIdx.y * npix;
+    }
     const int C8 = C >> 3;
-    const T* src = (PX && in_f32) ? nullptr : in + (ok ? pix : 0) * C;
+    const T* src = (PX && in_f32) ? nullptr : in + spix * C;
     float v[MAXV][8];
     float sum = 0.f;
 #pragma unroll
@@ -73,7 +82,7 @@ __global__ __launch_bounds__(256) void ln2d_kernel(const T* __restrict__ in, T* 
         const int c8 = sub + i * LPP;
         if (c8 < C8) {
             if (PX && in_f32) {
-                const float* sf = in_f32 + (ok ? pix : 0) * C + c8 * 8;
+                const float* sf = in_f32 + spix * C + c8 * 8;
                 const f4 t0 = *(const f4*)sf, t1 = *(const f4*)(sf + 4);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) { v[i][j] = t0[j]; v[i][4 + j] = t1[j]; }
@@ -84,7 +93,7 @@ __global__ __launch_bounds__(256) void ln2d_kernel(const T* __restrict__ in, T* 
 #pragma unroll
                 for (int j = 0; j < 8; ++j) v[i][j] = (float)t[j];
                 if (PX && in_lo) {
-                    const v8 tl = *((const v8*)(in_lo + (ok ? pix : 0) * C) + c8);
+                    const v8 tl = *((const v8*)(in_lo + spix * C) + c8);
 #pragma unroll
                     for (int j = 0; j < 8; ++j) v[i][j] += (float)tl[j];
                 }
@@ -186,6 +195,63 @@ int ln2d_launch(const T* in, T* out, const float* w, const float* b, float eps, 
     return check_launch("layernorm2d");
 }
 
+// ln2d_kernel<.., CROP>: grid (pixel groups of one image, images)
+template <typename T>
+int ln2d_crop_launch(const T* in, T* out, const float* w, const float* b, float eps, int B, int H, int W, int Hp, int Wp, int C, int Cv,
+                     hipStream_t stream) {
+    const int c8 = C / 8;
+    const int64_t npix = (int64_t)H * W;
+#define FVIT_LN2D_CROP(LPP, MAXV)                                                                                                          \
+    hipLaunchKernelGGL((ln2d_kernel<T, LPP, MAXV, false, true>), dim3((unsigned)((npix + 4 * (64 / LPP) - 1) / (4 * (64 / LPP))), (unsigned)B), \
+                       dim3(256), 0, stream, in, out, w, b, eps, npix, C, Cv, nullptr, nullptr, nullptr, W, Hp, Wp)
+    if (c8 <= 8) { FVIT_LN2D_CROP(8, 1); }
+    else if (c8 <= 16) { FVIT_LN2D_CROP(16, 1); }
+    else if (c8 <= 32) { FVIT_LN2D_CROP(32, 1); }
+    else if (c8 <= 64) { FVIT_LN2D_CROP(64, 1); }
+    else if (c8 <= 128) { FVIT_LN2D_CROP(64, 2); }
+    else if (c8 <= 256) { FVIT_LN2D_CROP(64, 4); }
+    else {
+        set_error("layernorm2d_crop: C=%d too wide (max 2048)", C);
+        return FVIT_EINVAL;
+    }
+#undef FVIT_LN2D_CROP
+    return check_launch("layernorm2d_crop");
+}
+
+// map_pad: out[b][y][x][:] = in[b][y][x][:] for y < H && x < W, else zeros; every 16-byte vector of the output written exactly once.  A row of the
+// padded map and the row of the dense map it copies start at different offsets but run in step (x * C + c), so the source of output vector v of a row
+// is vector v of the input row while v < W * C / 8: no division.  One thread moves the same vector of ROWS consecutive rows (loads first, then stores).
+template <typename T, int ROWS>
+__global__ __launch_bounds__(256) void map_pad_kernel(const T* __restrict__ in, T* __restrict__ out, int H, int W, int Hp, int Wp, int C) {
+    typedef T v8 __attribute__((ext_vector_type(8)));
+    const int v = blockIdx.x * 256 + threadIdx.x;   // vector within a row
+    const int nin = W * (C >> 3), nout = Wp * (C >> 3);
+    if (v >= nout) return;
+    const int b = blockIdx.z, y0 = blockIdx.y * ROWS;
+    v8 t[ROWS];
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) {
+        const int y = y0 + r;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) t[r][j] = (T)0.f;
+        if (y < H && v < nin) t[r] = *((const v8*)(in + ((int64_t)b * H + y) * W * C) + v);
+    }
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) {
+        const int y = y0 + r;
+        if (y < Hp) *((v8*)(out + ((int64_t)b * Hp + y) * Wp * C) + v) = t[r];
+    }
+}
+
+template <typename T>
+int map_pad_launch(const T* in, T* out, int B, int H, int W, int Hp, int Wp, int C, hipStream_t stream) {
+    constexpr int ROWS = 4;
+    const int64_t nout = (int64_t)Wp * (C / 8);
+    hipLaunchKernelGGL((map_pad_kernel<T, ROWS>), dim3((unsigned)((nout + 255) / 256), (unsigned)((Hp + ROWS - 1) / ROWS), (unsigned)B), dim3(256), 0,
+                       stream, in, out, H, W, Hp, Wp, C);
+    return check_launch("map_pad");
+}
+
 }  // namespace
 }  // namespace fvit
 
@@ -231,6 +297,36 @@ int fvit_layernorm2d_cl(int32_t dtype, const void* in, void* out, const float* w
     if (dtype == FVIT_F16) return ln2d_launch<_Float16>((const _Float16*)in, (_Float16*)out, weight, bias, eps, n_pixels, C, C_valid, (hipStream_t)stream);
     if (dtype == FVIT_BF16) return ln2d_launch<__bf16>((const __bf16*)in, (__bf16*)out, weight, bias, eps, n_pixels, C, C_valid, (hipStream_t)stream);
     set_error("layernorm2d: dtype %d not supported (16-bit maps only)", dtype);
+    return FVIT_EINVAL;
+}
+
+int fvit_layernorm2d_crop_cl(int32_t dtype, const void* in, void* out, const float* weight, const float* bias, float eps, int32_t B, int32_t H,
+                             int32_t W, int32_t Hp, int32_t Wp, int32_t C, int32_t C_valid, fvit_stream_t stream) {
+    if (C_valid <= 0) C_valid = C;
+    if (!in || !out || !weight || !bias || B <= 0 || B > 65535 || H <= 0 || W <= 0 || Hp < H || Wp < W || C <= 0 || (C % 8) || C_valid > C ||
+        (int64_t)H * W > INT32_MAX) {
+        set_error("layernorm2d_crop: bad arguments (B=%d <= 65535, crop %dx%d of a %dx%d map, C=%d must be a multiple of 8, C_valid=%d <= C)", B, H, W,
+                  Hp, Wp, C, C_valid);
+        return FVIT_EINVAL;
+    }
+    ProfScope prof(FVIT_K_OTHER, 0.0, 4.0 * B * H * W * C, (hipStream_t)stream);
+    if (dtype == FVIT_F16) return ln2d_crop_launch<_Float16>((const _Float16*)in, (_Float16*)out, weight, bias, eps, B, H, W, Hp, Wp, C, C_valid, (hipStream_t)stream);
+    if (dtype == FVIT_BF16) return ln2d_crop_launch<__bf16>((const __bf16*)in, (__bf16*)out, weight, bias, eps, B, H, W, Hp, Wp, C, C_valid, (hipStream_t)stream);
+    set_error("layernorm2d_crop: dtype %d not supported (16-bit maps only)", dtype);
+    return FVIT_EINVAL;
+}
+
+int fvit_map_pad_cl(int32_t dtype, const void* in, void* out, int32_t B, int32_t H, int32_t W, int32_t Hp, int32_t Wp, int32_t C,
+                    fvit_stream_t stream) {
+    if (!in || !out || B <= 0 || B > 65535 || H <= 0 || W <= 0 || Hp < H || Wp < W || (Hp + 3) / 4 > 65535 || C <= 0 || (C % 8) ||
+        (int64_t)Wp * (C / 8) > INT32_MAX) {
+        set_error("map_pad: bad arguments (B=%d <= 65535, %dx%d into %dx%d needs Hp >= H and Wp >= W, C=%d must be a multiple of 8)", B, H, W, Hp, Wp, C);
+        return FVIT_EINVAL;
+    }
+    ProfScope prof(FVIT_K_OTHER, 0.0, 2.0 * B * C * ((double)H * W + (double)Hp * Wp), (hipStream_t)stream);
+    if (dtype == FVIT_F16) return map_pad_launch<_Float16>((const _Float16*)in, (_Float16*)out, B, H, W, Hp, Wp, C, (hipStream_t)stream);
+    if (dtype == FVIT_BF16) return map_pad_launch<__bf16>((const __bf16*)in, (__bf16*)out, B, H, W, Hp, Wp, C, (hipStream_t)stream);
+    set_error("map_pad: dtype %d not supported (16-bit maps only)", dtype);
     return FVIT_EINVAL;
 }
 

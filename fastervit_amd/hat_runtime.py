@@ -723,6 +723,27 @@ def is_prepared(layer, device, batch: Optional[int] = None, hw=None, slots=(0,))
     return all(((batch, Hp, Wp, H, W, op_code, s) + (("x3",) if terms == 3 else ())) in st.workspaces for s in slots)
 
 
+def stage_refs(layer, device, batch: int, H: int, W: int, slot: int = 0) -> tuple:
+    """Strong references to everything a ``stage_forward`` call of ``layer`` on a (batch, C, H, W) map in workspace slot ``slot`` hands the kernels by
+    raw pointer: (index tables, packed weights, workspace, tokenizer weights).  Such a call must have run.  A dynamic-grid layer keeps these per
+    geometry in an LRU of ``DYN_CACHE_SIZE``; a captured graph holds their addresses, so its owner holds these references for as long as it replays
+    (eviction then drops only the cache's reference; a later eager call at this geometry builds its own)."""
+    st = _state(layer, device)
+    ws = layer.window_size
+    Hp, Wp = H + (ws - H % ws) % ws, W + (ws - W % ws) % ws
+    op_code, _, terms = _OP[getattr(layer, "hat_operand_dtype", "f16")]
+    dyn = bool(getattr(layer, "dynamic_grid", False)) and bool(layer.blocks[0].do_sr_hat)
+    with st.lock:
+        tables = st.tables.get((Hp, Wp))
+        pack = st.packs.get((Hp, Wp)) if dyn else (st.sig, st.keep, st.blocks_c)
+        wsp = st.workspaces.get((batch, Hp, Wp, H, W, op_code, int(slot)) + (("x3",) if terms == 3 else ()))
+    if tables is None or pack is None or pack[1] is None or wsp is None:
+        raise RuntimeError(f"stage_refs: no stage call of a {batch} x {H} x {W} map in workspace slot {slot} has run on {device}")
+    tok = getattr(layer, "global_tokenizer", None)
+    tokw = tok.__dict__.get("_fvit_tok", {}).get(str(device)) if tok is not None else None
+    return tables, pack, wsp, tokw
+
+
 def stage_forward(layer, x: torch.Tensor, tokenizer=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Transformer branch of FasterViTLayer.forward (AR:848-869) minus the Downsample.  ``x`` and the optional preallocated
     ``out`` (same shape and dtype) may be arbitrary strided views, e.g. the leading channels of a channel-padded map.

@@ -1,5 +1,6 @@
 """Library-level inference runners (replaces the eval loop plumbing of validate.py:243-344 for throughput runs).
 
+``CompiledBackboneInference``  the same runner over the detection backbone's plan: several output maps, pinned per-geometry stage state.
 ``CompiledInference``  one GPU: the deploy plan (BN folded, 16-bit channels_last conv side on the HIP conv kernels, HAT stages on
                        the HIP kernels) run as stream shards and captured into ONE hipGraph with static buffers -- the
                        configuration ``bench.py`` measures, as a reusable object instead of caller code.
@@ -33,10 +34,9 @@ class CompiledInference:
             raise RuntimeError("compile_inference: the example input must be on a HIP device (no CPU fallback)")
         if model.training:
             raise RuntimeError("compile_inference: call model.eval() first (inference-only path)")
-        from .conv_runtime import DeployPlan
         self.model = model
         self.device = example.device
-        self.plan = DeployPlan(model, dtype)
+        self.plan = self._make_plan(model, dtype)
         self.plan.streams = max(1, int(streams))
         # join_from = L: the shards run levels [0, L) on their streams, join, and levels [L, end) + head run once on the whole batch
         # (DeployPlan._forward_sharded).  FasterViT-0 at batch 256: streams = 2, join_from = 3 is the measured optimum (bench.py)
@@ -53,7 +53,18 @@ class CompiledInference:
         self.static_x = example.detach().clone()
         self.graph = None
         self.static_y = None
+        self.pins = None
         self.recompile()
+
+    @staticmethod
+    def _make_plan(model, dtype):
+        from .conv_runtime import DeployPlan
+        return DeployPlan(model, dtype)
+
+    def _pin(self):
+        """What the captured graph addresses but this runner does not own (``CompiledBackboneInference``); the classifier's stages have one geometry,
+        which ``hat_runtime`` never evicts."""
+        return None
 
     def recompile(self):
         with torch.no_grad(), torch.cuda.device(self.device):
@@ -67,23 +78,25 @@ class CompiledInference:
             torch.cuda.synchronize(self.device)
             if not self.use_graph:
                 self.graph, self.static_y = None, y
-                return
-            g = torch.cuda.CUDAGraph()   # a hipGraph on ROCm
-            with torch.cuda.graph(g):
-                self.static_y = self.plan.forward(self.static_x)
-            self.graph = g
-            torch.cuda.synchronize(self.device)
+            else:
+                g = torch.cuda.CUDAGraph()   # a hipGraph on ROCm
+                with torch.cuda.graph(g):
+                    self.static_y = self.plan.forward(self.static_x)
+                self.graph = g
+                torch.cuda.synchronize(self.device)
+            self.pins = self._pin()
 
     @property
     def max_batch(self) -> int:
         return self.static_x.shape[0]
 
-    def __call__(self, x: torch.Tensor) -> torch.Tensor:
+    def __call__(self, x: torch.Tensor):
+        name = type(self).__name__
         if not x.is_cuda or x.device != self.device:
-            raise RuntimeError(f"CompiledInference: input is on {x.device}, the runner was compiled for {self.device} (no implicit copy)")
+            raise RuntimeError(f"{name}: input is on {x.device}, the runner was compiled for {self.device} (no implicit copy)")
         n = x.shape[0]
         if tuple(x.shape[1:]) != tuple(self.static_x.shape[1:]) or n > self.max_batch:
-            raise RuntimeError(f"CompiledInference: input {tuple(x.shape)} does not fit the compiled shape {tuple(self.static_x.shape)}")
+            raise RuntimeError(f"{name}: input {tuple(x.shape)} does not fit the compiled shape {tuple(self.static_x.shape)}")
         with torch.no_grad(), torch.cuda.device(self.device):
             if n == self.max_batch:
                 self.static_x.copy_(x, non_blocking=True)
@@ -94,7 +107,46 @@ class CompiledInference:
                 self.graph.replay()
             else:
                 self.static_y = self.plan.forward(self.static_x)
+        if isinstance(self.static_y, tuple):   # a plan that returns several maps (the detection backbone)
+            return tuple(y[:n] for y in self.static_y)
         return self.static_y[:n]
+
+
+class CompiledBackboneInference(CompiledInference):
+    """``FasterViTBackbone.compile_inference(example)``: ``CompiledInference`` over ``conv_runtime.BackboneDeployPlan``.  ``runner(x)`` returns the tuple
+    of NCHW fp32 maps of ``forward_features``, ``runner.forward(tensor_list)`` the ``{k: NestedTensor}`` dict of ``FasterViTBackbone.forward``; both
+    are views of static buffers, overwritten by the next call (clone to keep).
+
+    * fixed to ``example``'s device, IMAGE SIZE and maximum batch: shorter batches are zero-padded, any other image size raises.  Detection pipelines
+      bucket their input sizes; compile one runner per bucket.
+    * pinning: the window grid follows the image size, and ``hat_runtime`` keeps the packed weights, tables and workspaces of a dynamic-grid stage in an
+      LRU of ``DYN_CACHE_SIZE`` geometries.  The captured graph holds raw pointers to them, so after its warm-up passes the runner takes strong references
+      to exactly the objects of its geometry (``runner.pins``) and keeps them for its lifetime; eager calls at other sizes evict only the cache's
+      reference, and an eager call at this geometry after an eviction builds its own.
+    * stream contract (as for ``CompiledInference``): the graph replays on the caller's current stream and shares the stage workspace of
+      (geometry, ``slot_base``) with eager calls at the same geometry and slot, whose cross-stream event bookkeeping a replay does not take part in.
+      Replays and such eager calls must be ordered on ONE stream; runners meant to overlap on different streams take different ``slot_base``.
+    * a weight update is not picked up by the graph; call ``recompile()``."""
+
+    def __init__(self, model, example: torch.Tensor, dtype=torch.float16, graph: bool = True, slot_base: int = 0, streams: int = 1, precise=None):
+        if precise:
+            raise NotImplementedError("compile_inference: precise=True is not implemented for the backbone (there is no two-term feature tap)")
+        if int(streams) > 1:
+            raise NotImplementedError("compile_inference: streams > 1 (stream shards) is not implemented for the backbone")
+        if dtype not in (torch.float16, torch.bfloat16):
+            raise ValueError("compile_inference: dtype must be torch.float16 or torch.bfloat16")
+        super().__init__(model, example, dtype=dtype, streams=1, graph=graph, slot_base=slot_base)
+
+    @staticmethod
+    def _make_plan(model, dtype):
+        from .conv_runtime import BackboneDeployPlan
+        return BackboneDeployPlan(model, dtype)
+
+    def _pin(self):
+        return self.plan.pinned(tuple(self.static_x.shape), self.device)
+
+    def forward(self, tensor_list):
+        return self.model._nested(self(tensor_list.tensors), tensor_list)
 
 
 def _masked_stream(device, mask_words):

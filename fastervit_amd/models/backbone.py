@@ -187,11 +187,34 @@ class FasterViTBackbone(HatSwitches, nn.Module):
             raise RuntimeError("FasterViTBackbone is inference-only and its outputs carry no gradient: run it under torch.no_grad() "
                                "(or torch.inference_mode()), or freeze its parameters and detach the input")
 
+    def switch_to_deploy(self, dtype=torch.float16):
+        """Opt-in inference plan (``fastervit_amd.conv_runtime.BackboneDeployPlan``): BatchNorm folded into the conv weights, 16-bit
+        channels_last conv-side maps on the HIP conv kernels, ``norm{i}`` folded into the feature tap.  ``forward_features`` / ``forward`` use it wherever
+        they take the inference branch (eval mode; with ``enable_hat_backward`` on: under ``torch.no_grad()``); the grad and train paths are untouched.
+        A weight change is picked up by the next call.  ``dtype``: ``torch.float16`` or ``torch.bfloat16``; ``None`` returns to module mode."""
+        if dtype is None:
+            self.__dict__.pop("_deploy_plan", None)
+            return self
+        from ..conv_runtime import BackboneDeployPlan
+        self.__dict__["_deploy_plan"] = BackboneDeployPlan(self, dtype)
+        return self
+
+    def compile_inference(self, example: torch.Tensor, dtype=torch.float16, graph: bool = True, slot_base: int = 0, streams: int = 1, precise=None):
+        """The deploy plan captured ONCE into a hipGraph with static buffers, for ``example``'s device, image size and maximum batch (shorter batches are
+        zero-padded; another image size raises): ``runner(x)`` -> the tuple of ``forward_features``, ``runner.forward(tensor_list)`` -> the dict of
+        ``forward``.  One runner per input-size bucket.  See ``fastervit_amd.inference.CompiledBackboneInference``."""
+        from ..inference import CompiledBackboneInference
+        return CompiledBackboneInference(self, example, dtype=dtype, graph=graph, slot_base=slot_base, streams=streams, precise=precise)
+
     def forward_features(self, x: torch.Tensor):
         """Tuple of the ``out_indices`` levels' normalised pre-downsample maps, NCHW fp32."""
         if self._wants_grad_path(x):
             return self._forward_features_grad(x)
         self._check_inference(x)
+        plan = self.__dict__.get("_deploy_plan")
+        if plan is not None and not getattr(self, "_is_replica", False):
+            with torch.no_grad():
+                return plan.forward(x)
         from ..hat_runtime import feature_tap
         with torch.no_grad():
             x = self.patch_embed(x)
@@ -203,7 +226,11 @@ class FasterViTBackbone(HatSwitches, nn.Module):
         return tuple(outs)
 
     def forward(self, tensor_list):
-        outs = self.forward_features(tensor_list.tensors)
+        return self._nested(self.forward_features(tensor_list.tensors), tensor_list)
+
+    @staticmethod
+    def _nested(outs, tensor_list):
+        """``{k: NestedTensor(feature, mask interpolated to the feature's size)}`` of the returned levels."""
         m = tensor_list.mask
         if m is None:
             raise ValueError("FasterViTBackbone.forward: tensor_list.mask is None")

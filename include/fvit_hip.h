@@ -443,6 +443,18 @@ int fvit_bias_residual_cl(int32_t dtype, void* x, const void* y, const float* bi
  * on input (channel-padded deploy maps) and weight / bias must be zero there, so they stay zero on output. */
 int fvit_layernorm2d_cl(int32_t dtype, const void* in, void* out, const float* weight, const float* bias, float eps,
                         int64_t n_pixels, int32_t C, int32_t C_valid, fvit_stream_t stream);
+/* The two passes the detection backbone's deploy plan adds (fastervit_amd/conv_runtime.py: BackboneDeployPlan), 16-bit channels_last maps, C % 8 == 0,
+ * 16-byte accesses, 64-bit element offsets.  Caller-owned memory and stream; no allocation, no host synchronisation, no atomics; a repeated call
+ * returns the same bits.  B <= 65535.
+ * map_pad: in [B][H][W][C] -> out [B][Hp][Wp][C] (Hp >= H, Wp >= W): every output pixel is written exactly once, the input pixel where
+ * y < H && x < W and zeros elsewhere (one pass; Hp == H && Wp == W is a copy). */
+int fvit_map_pad_cl(int32_t dtype, const void* in, void* out, int32_t B, int32_t H, int32_t W, int32_t Hp, int32_t Wp, int32_t C,
+                    fvit_stream_t stream);
+/* layernorm2d_crop: the dense LayerNorm2d pass above on the H x W corner of a padded map -- input pixel (b, y, x) at ((b * Hp + y) * Wp + x) * C
+ * of in, output the dense [B][H][W][C] map.  The per-pixel body is the dense kernel's (fp32 statistics, the same reduction order, C_valid and pad
+ * channels as there): for the same pixels the output is bitwise what the dense pass gives on a contiguous copy of the crop. */
+int fvit_layernorm2d_crop_cl(int32_t dtype, const void* in, void* out, const float* weight, const float* bias, float eps, int32_t B, int32_t H,
+                             int32_t W, int32_t Hp, int32_t Wp, int32_t C, int32_t C_valid, fvit_stream_t stream);
 
 /* AdaptiveAvgPool2d(1) + flatten (FV:926, 955-956) of a channels-last map: out f32 [B][C] = mean over the HW pixels of in [B][HW][C] (fp32 / fp16 / bf16),
  * fp32 sums in a fixed order (bitwise repeatable).  With fvit_head_logits the tail of the deploy plan: no library kernel in the timed graph. */

@@ -11,7 +11,13 @@ forward run level by level (stem, then each level including its feature tap).
 
 times one fine-tuning step instead (``enable_hat_backward().train()``: train-mode forward + backward + AdamW, batch-statistics BatchNorm,
 drop_path_rate of the configuration) at the same sizes, and the two backward kernels of the backbone alone (fvit_token_init_dyn_backward,
-fvit_feature_tap_backward) next to PyTorch autograd of the same ops on the same device; the JSON lines are also written to ``--out``."""
+fvit_feature_tap_backward) next to PyTorch autograd of the same ops on the same device; the JSON lines are also written to ``--out``.
+
+    python scripts/bench_backbone.py --deploy [--out profiles/bench_backbone_deploy.json]
+
+times, for each size and in one process, module mode, eager deploy (``switch_to_deploy()``) and the graph runner (``compile_inference``) in
+interleaved rounds, the per-level times of eager deploy, and the two glue kernels of the plan alone on the level-0 map of that size
+(fvit_map_pad_cl, fvit_layernorm2d_crop_cl next to the dense fvit_layernorm2d_cl on the same pixel count) with their bytes moved and GB/s."""
 import argparse
 import json
 import os
@@ -129,10 +135,108 @@ def bench_train(a, dev):
             f.write("\n")
 
 
+def per_level_deploy(plan, x):
+    """Event intervals of one eager-deploy forward run step by step: stem, then each level with its tap and Downsample."""
+    from fastervit_amd import hat_runtime
+    from fastervit_amd.conv_runtime import LevelMap
+    plan._enter(x)
+    plan._refresh()
+    levels, taps = plan.model.levels, plan.t["taps"]
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(levels) + 2)]
+    with hat_runtime.workspace_slot(plan.slot_base):
+        ev[0].record()
+        y = plan._stem(x)
+        m = LevelMap(y, y.shape[2], y.shape[3])
+        ev[1].record()
+        for li, (lvl, e) in enumerate(zip(levels, plan.t["levels"])):
+            m = plan._conv_level_padded(m, e["blocks"], lvl.window_size) if "blocks" in e else plan._hat_level_dyn(lvl, m, padded_out="down" in e)
+            if li in taps:
+                plan._tap(m, taps[li])
+            if "down" in e:
+                m = plan._downsample_crop(m, e["down"])
+            ev[li + 2].record()
+    torch.cuda.synchronize()
+    return {"stem_ms": ev[0].elapsed_time(ev[1]), **{f"level{i}_ms": ev[i + 1].elapsed_time(ev[i + 2]) for i in range(len(levels))}}
+
+
+def glue_kernels(a, dev, H, W, dtype=torch.float16):
+    """fvit_map_pad_cl and fvit_layernorm2d_crop_cl alone on the level-0 map of an H x W image (window 7), and the dense LayerNorm2d kernel on the same
+    pixel count.  Bytes are what each pass must move (read + write, 16-bit); the roof is bytes over HBM bandwidth."""
+    import ctypes
+    from fastervit_amd import _lib
+    lib, code = _lib.lib(), _lib.FVIT_F16
+    st = torch.cuda.current_stream().cuda_stream
+    B, C = a.batch, 64
+    h, w = -(-H // 4), -(-W // 4)
+    hp, wp = -(-h // 7) * 7, -(-w // 7) * 7
+    x = torch.randn(B, h, w, C, device=dev).to(dtype)
+    xp = torch.empty(B, hp, wp, C, device=dev, dtype=dtype)
+    out = torch.empty_like(x)
+    g, b = torch.ones(C, device=dev), torch.zeros(C, device=dev)
+    eps = ctypes.c_float(1e-6)
+    rows = []
+    for what, fn, nbytes in [
+            ("fvit_map_pad_cl", lambda: lib.fvit_map_pad_cl(code, x.data_ptr(), xp.data_ptr(), B, h, w, hp, wp, C, st), 2 * B * C * (h * w + hp * wp)),
+            ("fvit_layernorm2d_crop_cl", lambda: lib.fvit_layernorm2d_crop_cl(code, xp.data_ptr(), out.data_ptr(), g.data_ptr(), b.data_ptr(), eps, B, h, w,
+                                                                             hp, wp, C, C, st), 4 * B * C * h * w),
+            ("fvit_layernorm2d_cl", lambda: lib.fvit_layernorm2d_cl(code, x.data_ptr(), out.data_ptr(), g.data_ptr(), b.data_ptr(), eps, B * h * w, C, C, st),
+             4 * B * C * h * w)]:
+        assert fn() == 0, lib.fvit_last_error()
+        us = event_us(fn, 200, 20)
+        rows.append({"what": what, "map": [B, h, w, C], "padded": [hp, wp], "us": round(us, 2), "bytes": nbytes, "GB_per_s": round(nbytes / us * 1e-3, 1),
+                     "hbm_roof_us_at_6.3TBps": round(nbytes / 6.3e6, 2)})
+    return rows
+
+
+def bench_deploy(a, dev):
+    out_indices = (1, 2, 3)
+    rows = []
+
+    def build():
+        m = fastervit_amd.build_fastervit(a.model, out_indices=out_indices)
+        m.load_state_dict(synth_state_dict(m.state_dict(), 0, "init"))
+        return m.eval().to(dev).requires_grad_(False)
+
+    module, deploy = build(), build().switch_to_deploy()
+    for size in a.sizes.split(","):
+        H, W = (int(v) for v in size.split("x"))
+        x = synth_input(a.batch, H, W, 0).to(dev)
+        with torch.no_grad():
+            runner = deploy.compile_inference(x)
+            forms = {"module": lambda: module.forward_features(x), "eager_deploy": lambda: deploy.forward_features(x), "runner": lambda: runner(x)}
+            ref = forms["module"]()
+            err = {k: max(((g - r).abs().max() / r.abs().max()).item() for g, r in zip(forms[k](), ref)) for k in ("eager_deploy", "runner")}
+            times = {k: [] for k in forms}
+            for _ in range(a.rounds):   # interleaved: every form sees the same machine state
+                for k, fn in forms.items():
+                    times[k].append(timed(fn, a.steps, a.warmup) * 1e3)
+            levels = per_level_deploy(deploy.__dict__["_deploy_plan"], x)
+            levels_module = per_level(module, x)
+        med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+        rows.append({"what": "forward_features", "model": a.model, "size": [H, W], "batch": a.batch, "dtype": "float16", "operands": "f16",
+                     "ms": {k: round(v, 3) for k, v in med.items()}, "ms_rounds": {k: [round(t, 3) for t in v] for k, v in times.items()},
+                     "speedup_vs_module": {k: round(med["module"] / med[k], 2) for k in ("eager_deploy", "runner")},
+                     "per_level_ms_eager_deploy": {k: round(v, 3) for k, v in levels.items()},
+                     "per_level_ms_module": {k: round(v, 3) for k, v in levels_module.items()},
+                     "max_rel_diff_vs_module": {k: float(f"{v:.3e}") for k, v in err.items()}})
+        print(json.dumps(rows[-1]), flush=True)
+        for r in glue_kernels(a, dev, H, W):
+            r["share_of_level0"] = round(r["us"] * 1e-3 / levels["level0_ms"], 4)
+            rows.append(r)
+            print(json.dumps(r), flush=True)
+        del runner
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump({"device": torch.cuda.get_device_name(0), "steps": a.steps, "warmup": a.warmup, "rounds": a.rounds, "rows": rows}, f, indent=1)
+            f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--deploy", action="store_true", help="time module mode, eager deploy and the graph runner, and the plan's two glue kernels")
+    ap.add_argument("--rounds", type=int, default=3, help="with --deploy: interleaved timing rounds per form (the median is reported)")
     ap.add_argument("--train", action="store_true", help="time one fine-tuning step and the two backward kernels instead of the inference forward")
-    ap.add_argument("--out", default="", help="with --train: also write the result rows to this JSON file")
+    ap.add_argument("--out", default="", help="with --train / --deploy: also write the result rows to this JSON file")
     ap.add_argument("--model", default="faster_vit_0_224")
     ap.add_argument("--batch", type=int, default=2)
     ap.add_argument("--steps", type=int, default=20)
@@ -143,6 +247,8 @@ def main():
     dev = "cuda:0"
     if a.train:
         return bench_train(a, dev)
+    if a.deploy:
+        return bench_deploy(a, dev)
     out_indices = (1, 2, 3)
     model = fastervit_amd.build_fastervit(a.model, out_indices=out_indices)
     sd = synth_state_dict(model.state_dict(), 0, "init")
