@@ -40,6 +40,7 @@ EXPORTED_SYMBOLS = (
     "fvit_bwd_colsum_finish", "fvit_bwd_colsum16", "fvit_bwd_window_attention", "fvit_bwd_window_attention_long",
     "fvit_bwd_window_attention_long_workspace", "fvit_tune", "fvit_prof_enable", "fvit_prof_collect",
     "fvit_prof_records", "fvit_prof_kind_name",
+    "fvit_hat_stage_forward_tail", "fvit_rows_avgpool", "fvit_conv3x3_c64_ln2d", "fvit_conv3x3_c128_band_ln2d",
 )
 # only in libfvit_hip_diag.so (the same sources with -DFVIT_DIAG; FVIT_DIAG=1 selects it): diagnosis entry points of include/fvit_hip.h's #ifdef FVIT_DIAG
 # section.  The shipped library exports none of them and compiles the ablation knobs out (tests/test_abi.py).
@@ -79,6 +80,10 @@ class FvitBlockWeights(C.Structure):
 
 class FvitStageTables(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("ln1_src", "ln1_add", "ct_src", "up_idx")]
+
+
+class FvitStageTail(C.Structure):
+    _fields_ = [("ln_w", C.c_void_p), ("ln_b", C.c_void_p), ("pool_out", C.c_void_p), ("ln_eps", C.c_float), ("pool_dtype", C.c_int32)]
 
 
 class FvitMapView(C.Structure):
@@ -123,6 +128,15 @@ def _declare(lib):
     lib.fvit_hat_stage_forward.argtypes = [C.POINTER(FvitStageDesc), C.POINTER(FvitBlockWeights),
                                            C.POINTER(FvitStageTables), C.POINTER(FvitMapView), vp,
                                            C.POINTER(FvitMapView), vp, C.c_size_t, vp]
+    lib.fvit_hat_stage_forward_tail.restype = C.c_int
+    lib.fvit_hat_stage_forward_tail.argtypes = [C.POINTER(FvitStageDesc), C.POINTER(FvitBlockWeights),
+                                                C.POINTER(FvitStageTables), C.POINTER(FvitMapView), vp,
+                                                C.POINTER(FvitMapView), C.POINTER(FvitStageTail), vp, C.c_size_t, vp]
+    lib.fvit_rows_avgpool.restype = C.c_int
+    lib.fvit_rows_avgpool.argtypes = [i32, vp, vp, i32, i32, i32, vp]
+    for fn in (lib.fvit_conv3x3_c64_ln2d, lib.fvit_conv3x3_c128_band_ln2d):
+        fn.restype = C.c_int
+        fn.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, f32, i32, i32, i32, vp, vp]
     lib.fvit_hat_block_forward.restype = C.c_int
     lib.fvit_hat_block_forward.argtypes = [C.POINTER(FvitStageDesc), C.POINTER(FvitBlockWeights),
                                            C.POINTER(FvitStageTables), vp, vp, vp, C.c_size_t, vp]

@@ -14,7 +14,10 @@ per-forward path:
     implicit-GEMM, halo-tiled 64-channel conv, fused two-conv stem); channel counts that are not a multiple of 64 are
     zero-padded to one (``pad_channels``).  MIOpen (``F.conv2d``) + the glue passes of csrc/fvit_glue.hip remain only as the
     fallback for shapes those kernels do not cover (``pad_channels = False`` or ``use_hip_conv = False``).
-  * timm's LayerNorm2d (Downsample) is one HBM pass (``ln2d_kernel``).
+  * timm's LayerNorm2d (Downsample) is one HBM pass (``ln2d_kernel``) -- or, in the 16-bit classifier plan, no pass at all: it runs in the epilogue of
+    the kernel that produces the level's last map (the residual conv of the last ConvBlock, the window_reverse of a transformer level), from the
+    rounded 16-bit values that kernel would have stored (``fuse_conv_ln2d`` / ``fuse_reverse_ln2d``).  A one-window last level is pooled straight
+    from its token rows (``fuse_pool``): the mean over a window's tokens does not depend on their order.
   * The transformer stages are the same ``fvit_hat_stage_forward`` calls as in module mode.
 
   * ``plan.precise = True`` (r05; ``compile_inference(..., precise=True)``): the plan that meets north_star's ABSOLUTE logits bar on the deep / wide
@@ -140,6 +143,11 @@ class DeployPlan:
         # 196- / 392-channel maps (stored as 256 / 448).  Same products in the same order per tap; "0" = the classic [Cout][3][3][Cin padded] matrix
         self.dense_k = os.environ.get("FVIT_CONV_DENSE_K", "1") != "0"
         self.fused_stem = os.environ.get("FVIT_NO_FUSED_STEM", "0") != "1"   # both PatchEmbed convs in one kernel when in_dim == dim == 64 (the 112x112x64 map never reaches HBM)
+        # the level-glue fusions of the 16-bit plan (module docstring).  Each is taken only where the map is unpadded (c_valid == C) and
+        # its kernel covers the shape; the standalone passes remain everywhere else.  Keys of fuse_conv_ln2d: the level's channel count.
+        self.fuse_conv_ln2d = {64: os.environ.get("FVIT_FUSE_CONV64_LN2D", "1") != "0", 128: os.environ.get("FVIT_FUSE_CONV128_LN2D", "1") != "0"}
+        self.fuse_reverse_ln2d = os.environ.get("FVIT_FUSE_REVERSE_LN2D", "1") != "0"
+        self.fuse_pool = os.environ.get("FVIT_FUSE_POOL", "1") != "0"
 
     # ---- folding -------------------------------------------------------------------------
     def _signature(self):
@@ -216,6 +224,29 @@ class DeployPlan:
         if w.wk_classic is not None and _lib.lib().fvit_conv3x3_patch_form(B, Hi, Wi, Ci, Co, stride):
             wk, cv = w.wk_classic, Ci   # 8 x 16 patches + halo tiles (r06): the classic [Cout][terms][3][3][Cin] rows
         return wk, cv, Co, (Hi - 1) // stride + 1, (Wi - 1) // stride + 1
+
+    def _conv_ln2d_route(self, x, w: ConvWeight, d: "DownW"):
+        """Which kernel runs a level's last residual conv on the map x WITH the Downsample's LayerNorm2d in its epilogue: 'halo' (64 channels), 'band'
+        (128 channels, maps the row-band kernel takes), or None = the conv and the LayerNorm2d pass apart."""
+        C_ = x.shape[1]
+        if self.precise or not self.use_hip_conv or not self.fuse_conv_ln2d.get(C_, False) or d.cin != C_ or w.wk is None or w.terms != 1 \
+                or w.wk_classic is not None or not x.is_contiguous(memory_format=torch.channels_last):
+            return None
+        lib = _lib.lib()
+        if C_ == 64 and tuple(w.wk.shape) == (64, 3, 3, 64):
+            return "halo"
+        if C_ == 128 and w.wband is not None and lib.fvit_conv3x3_c128_band_supported(x.shape[2], x.shape[3]):
+            return "band"
+        return None
+
+    def _conv_ln2d(self, route, x, w: ConvWeight, bias, residual, d: "DownW"):
+        """LayerNorm2d(conv3x3(x, w) + bias + residual), in place on the residual: one kernel (``_conv_ln2d_route``)."""
+        B, _, Hi, Wi = x.shape
+        fn, wt, name = ((_lib.lib().fvit_conv3x3_c64_ln2d, w.wk, "fvit_conv3x3_c64_ln2d") if route == "halo" else
+                        (_lib.lib().fvit_conv3x3_c128_band_ln2d, w.wband, "fvit_conv3x3_c128_band_ln2d"))
+        _lib.check(fn(self.code, x.data_ptr(), wt.data_ptr(), bias.data_ptr() if bias is not None else None, residual.data_ptr(), residual.data_ptr(),
+                      d.ln_w.data_ptr(), d.ln_b.data_ptr(), d.eps, B, Hi, Wi, self._zero_page(x.device), _stream(self.dev)), name)
+        return residual
 
     def _conv(self, x, w: ConvWeight, bias, stride, act, residual=None):
         """act(conv3x3(x, w) + bias) (+ residual): one fused HIP kernel when supported, else MIOpen conv + glue passes."""
@@ -327,11 +358,16 @@ class DeployPlan:
             feat = torch.empty((B, C), dtype=torch.float32, device=x.device)
             _lib.check(_lib.lib().fvit_global_avgpool_cl(hat_runtime._DT[x.dtype], x.data_ptr(), feat.data_ptr(), B, H * W, C, _stream(self.dev)),
                        "fvit_global_avgpool_cl")
-            out = torch.empty((B, hw.shape[0]), dtype=torch.float32, device=x.device)
-            _lib.check(_lib.lib().fvit_head_logits(feat.data_ptr(), hw.data_ptr(), hb.data_ptr(), out.data_ptr(), B, hw.shape[0], C, _stream(self.dev)),
-                       "fvit_head_logits")
-            return out
+            return self._head_logits(feat, hw, hb)
         return F.linear(x.float().mean(dim=(2, 3)), hw, hb)
+
+    def _head_logits(self, feat, hw, hb):
+        """The head on (B, C) fp32 pooled features: fvit_head_logits (exact-fp32 MFMA)."""
+        B, C = feat.shape
+        out = torch.empty((B, hw.shape[0]), dtype=torch.float32, device=feat.device)
+        _lib.check(_lib.lib().fvit_head_logits(feat.data_ptr(), hw.data_ptr(), hb.data_ptr(), out.data_ptr(), B, hw.shape[0], C, _stream(self.dev)),
+                   "fvit_head_logits")
+        return out
 
     def _ln2d(self, x, w, b, eps, c_valid=None):
         """LayerNorm2d over the first c_valid (default: all) channels of a channels_last map; pad channels stay zero."""
@@ -493,10 +529,19 @@ class DeployPlan:
             for li, (lvl, e) in enumerate(zip(levels, self.t["levels"])):
                 if li < lv_from or (lv_to is not None and li >= lv_to):
                     continue
-                x = self._conv_level(x, e["blocks"]) if "blocks" in e else self._hat_level(lvl, x, padded_out="down" in e)
+                # normed: the level's kernels already applied the Downsample's LayerNorm2d; pooled: x is the (B, C) pooled features, not a map
+                normed = pooled = False
+                if "blocks" in e:
+                    x, normed = self._conv_level(x, e["blocks"], e.get("down"))
+                elif self._pool_tail(lvl, x, last=li + 1 == len(levels) and lv_to is None and "down" not in e):
+                    x, pooled = self._hat_level_pooled(lvl, x), True
+                else:
+                    x, normed = self._hat_level(lvl, x, padded_out="down" in e, down=e.get("down"))
                 if "down" in e:
-                    x = self._downsample(x, e["down"], f32_out=li + 1 < len(levels) and levels[li + 1].transformer_block)
-            return x if lv_to is not None else self._head(x)
+                    x = self._downsample(x, e["down"], f32_out=li + 1 < len(levels) and levels[li + 1].transformer_block, normed=normed)
+            if lv_to is not None:
+                return x
+            return self._head_logits(x, *self.t["head"][:2]) if pooled else self._head(x)
 
     def _stem(self, x):
         """PatchEmbed: conv + BN + ReLU twice, from the caller's image to the map level 0 takes."""
@@ -535,13 +580,19 @@ class DeployPlan:
         x = x.to(self.dtype).contiguous(memory_format=torch.channels_last)
         return self._conv(self._conv(x, st.conv0, st.bias0, 2, 1), st.conv1, st.bias1, 2, 1)
 
-    def _conv_level(self, x, blocks):
-        """The ConvBlocks of a level, in place on the stream."""
+    def _conv_level(self, x, blocks, down: Optional["DownW"] = None):
+        """The ConvBlocks of a level, in place on the stream -> (map, normed).  ``down``: the following Downsample; where the last conv's kernel can
+        (``_conv_ln2d_route``) it applies that Downsample's LayerNorm2d in its epilogue and ``normed`` is True."""
         if not self.precise:
-            for b in blocks:
+            normed = False
+            for i, b in enumerate(blocks):
                 y = self._conv(x, b.conv1, b.bias1, 1, 2)
-                x = self._conv(y, b.conv2, b.bias2, 1, 0, residual=x)
-            return x
+                route = self._conv_ln2d_route(y, b.conv2, down) if (down is not None and i + 1 == len(blocks)) else None
+                if route is not None:
+                    x, normed = self._conv_ln2d(route, y, b.conv2, b.bias2, x, down), True
+                else:
+                    x = self._conv(y, b.conv2, b.bias2, 1, 0, residual=x)
+            return x, normed
         hi, lo, f32 = x
         if hi is None:   # a conv level behind a transformer level (no reference entrypoint does this): split the fp32 map
             hi = f32.to(self.dtype)
@@ -549,11 +600,24 @@ class DeployPlan:
         for b in blocks:
             y, _ = self._conv_px(hi, None, b.conv1, b.bias1, 1, 2, want="single")              # conv1 + BN + GELU: an operand, one term
             hi, lo = self._conv_px(y, None, b.conv2, b.bias2, 1, 0, res=hi, res_lo=lo)         # conv2 + BN (+ gamma) + residual, in place on the stream
-        return hi, lo, None
+        return (hi, lo, None), False
 
-    def _hat_level(self, lvl, x, padded_out, tokenizer=None):
-        """A transformer level (``hat_runtime.stage_forward``) on a 16-bit map, or -- precise plan -- from and to an fp32 map.  ``tokenizer``: passed on
-        (the detection backbone's per-call TokenInitializer)."""
+    def _pool_tail(self, lvl, x, last):
+        """The last level hands its token rows straight to the pool (``hat_runtime.stage_forward(..., pool_out=)``): 16-bit plan, the final norm folded
+        into the head (BatchNorm), one window per image, no carrier tokens, unpadded channels."""
+        return (last and self.fuse_pool and not self.precise and self.t["head"].ln is None and torch.is_tensor(x) and len(lvl.blocks) > 0
+                and x.shape[1] == lvl.blocks[0].attn.qkv.in_features and x.shape[1] % 16 == 0 and self.t["head"].w.shape[1] == x.shape[1]
+                and hat_runtime.pool_tail_supported(lvl, x))
+
+    def _hat_level_pooled(self, lvl, x):
+        """The last transformer level -> (B, C) fp32 pooled features (``_pool_tail``)."""
+        feat = torch.empty((x.shape[0], x.shape[1]), dtype=torch.float32, device=x.device)
+        return hat_runtime.stage_forward(lvl, x, pool_out=feat)
+
+    def _hat_level(self, lvl, x, padded_out, tokenizer=None, down: Optional["DownW"] = None):
+        """A transformer level (``hat_runtime.stage_forward``) on a 16-bit map, or -- precise plan -- from and to an fp32 map -> (map, normed).
+        ``tokenizer``: passed on (the detection backbone's per-call TokenInitializer).  ``down``: the following Downsample; on an unpadded 16-bit map
+        the stage's window_reverse applies its LayerNorm2d (``normed`` True)."""
         if self.precise:
             hi, lo, x = x
             if x is None:   # a transformer level behind a conv level without a Downsample in between (no reference entrypoint does this)
@@ -570,14 +634,18 @@ class DeployPlan:
         if cpo != creal:
             xo[:, creal:] = 0   # only the pad channels need initialising; the stage writes the first creal
             hat_runtime.stage_forward(lvl, xin, tokenizer=tokenizer, out=xo[:, :creal])  # TokenInitializer: fvit_token_init in both modes
-        else:
-            xo = hat_runtime.stage_forward(lvl, xin, tokenizer=tokenizer, out=xo)
-        return (None, None, xo) if self.precise else xo
+            return ((None, None, xo) if self.precise else xo), False
+        if (down is not None and self.fuse_reverse_ln2d and not self.precise and down.cin == creal and len(lvl.blocks)
+                and hat_runtime.ln2d_tail_supported(xin, xo)):
+            return hat_runtime.stage_forward(lvl, xin, tokenizer=tokenizer, out=xo, ln2d=(down.ln_w, down.ln_b, down.eps)), True
+        xo = hat_runtime.stage_forward(lvl, xin, tokenizer=tokenizer, out=xo)
+        return ((None, None, xo) if self.precise else xo), False
 
-    def _downsample(self, x, d: DownW, f32_out):
-        """Downsample: LayerNorm2d + strided bias-free conv.  ``f32_out``: a transformer level follows, which the precise plan feeds an fp32 map."""
+    def _downsample(self, x, d: DownW, f32_out, normed=False):
+        """Downsample: LayerNorm2d + strided bias-free conv.  ``f32_out``: a transformer level follows, which the precise plan feeds an fp32 map.
+        ``normed``: the level's last kernel applied the LayerNorm2d already."""
         if not self.precise:
-            return self._conv(self._ln2d(x, d.ln_w, d.ln_b, d.eps, d.cin), d.conv, None, 2, 0)
+            return self._conv(x if normed else self._ln2d(x, d.ln_w, d.ln_b, d.eps, d.cin), d.conv, None, 2, 0)
         hi, lo, f32 = x
         if f32 is not None and not f32.is_contiguous(memory_format=torch.channels_last):
             f32 = f32.contiguous(memory_format=torch.channels_last)
@@ -692,7 +760,7 @@ class BackboneDeployPlan(DeployPlan):
         if (Hp, Wp) != (H, W) and len(blocks):
             x = torch.empty((B, C, Hp, Wp), dtype=self.dtype, device=m.x.device, memory_format=torch.channels_last)
             _lib.check(_lib.lib().fvit_map_pad_cl(self.code, m.x.data_ptr(), x.data_ptr(), B, H, W, Hp, Wp, C, _stream(self.dev)), "fvit_map_pad_cl")
-        return LevelMap(self._conv_level(x, blocks), H, W)
+        return LevelMap(self._conv_level(x, blocks)[0], H, W)
 
     def _hat_level_dyn(self, lvl, m: LevelMap, padded_out: bool) -> LevelMap:
         """A transformer level with the window grid and TokenInitializer pooling of THIS map size; dense in, dense out."""
@@ -700,7 +768,7 @@ class BackboneDeployPlan(DeployPlan):
         tok = None
         if len(lvl.blocks) and lvl.do_gt and lvl.blocks[0].do_sr_hat:
             tok = lambda xp: hat_runtime.token_init_dyn(lvl.global_tokenizer, xp, lvl.window_size)   # noqa: E731
-        return LevelMap(self._hat_level(lvl, m.x, padded_out, tokenizer=tok), m.H, m.W)
+        return LevelMap(self._hat_level(lvl, m.x, padded_out, tokenizer=tok)[0], m.H, m.W)
 
     def _tap(self, m: LevelMap, tw: TapW) -> torch.Tensor:
         """``norm{i}`` of the H x W corner's real channels -> contiguous NCHW fp32 (fvit_feature_tap reads the crop through strides)."""

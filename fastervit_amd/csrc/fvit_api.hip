@@ -601,9 +601,29 @@ int fvit_workspace_init(const FvitStageDesc* desc, void* workspace, size_t bytes
 int fvit_hat_stage_forward(const FvitStageDesc* desc, const FvitBlockWeights* blocks, const FvitStageTables* tables,
                            const FvitMapView* in, const float* ct_init, const FvitMapView* out, void* workspace,
                            size_t workspace_bytes, fvit_stream_t stream) {
+    return fvit_hat_stage_forward_tail(desc, blocks, tables, in, ct_init, out, nullptr, workspace, workspace_bytes, stream);
+}
+
+int fvit_rows_avgpool(int32_t round_dtype, const float* x, float* out, int32_t B, int32_t rows, int32_t C, fvit_stream_t stream) {
+    return launch_rows_avgpool(x, out, B, rows, C, round_dtype, (hipStream_t)stream);
+}
+
+int fvit_hat_stage_forward_tail(const FvitStageDesc* desc, const FvitBlockWeights* blocks, const FvitStageTables* tables,
+                                const FvitMapView* in, const float* ct_init, const FvitMapView* out, const FvitStageTail* tail,
+                                void* workspace, size_t workspace_bytes, fvit_stream_t stream) {
     StageLayout L;
-    FVIT_TRY(check_hat_call(desc, blocks && in && out, tables, workspace, workspace_bytes, ct_init, "hierarchical stage needs ct_init", L));
+    const bool pooled = tail && tail->pool_out;
+    FVIT_TRY(check_hat_call(desc, blocks && in && (out || pooled), tables, workspace, workspace_bytes, ct_init, "hierarchical stage needs ct_init", L));
     const FvitStageDesc& d = *desc;
+    if (tail && (!tail->ln_w != !tail->ln_b || (pooled && tail->ln_w))) {
+        set_error("stage tail: LayerNorm2d needs both ln_w and ln_b, and excludes pool_out");
+        return FVIT_EINVAL;
+    }
+    if (pooled && (d.hier || L.nW != 1 || L.ncw != 0 || d.H != d.Hp || d.W != d.Wp)) {
+        set_error("stage tail: pool_out needs one window per image and no carrier tokens (hier=%d, %d windows, map %dx%d of %dx%d)", d.hier, L.nW, d.H, d.W,
+                  d.Hp, d.Wp);
+        return FVIT_EINVAL;
+    }
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     float* X = (float*)(ws + L.off_X);
@@ -622,9 +642,12 @@ int fvit_hat_stage_forward(const FvitStageDesc* desc, const FvitBlockWeights* bl
         }
     }
     for (int i = 0; i < d.depth; ++i) FVIT_TRY(run_block(d, L, routes[i], blocks[i], *tables, ws, st));
+    if (pooled)   // the only consumer is the global average pool, which does not care about the token order: no reverse, no map
+        return launch_rows_avgpool(X, tail->pool_out, d.batch, L.S, d.C, tail->pool_dtype, st);
     const bool prop = d.hier && d.do_propagation && d.depth > 0 && blocks[d.depth - 1].last;
     ReverseCall rc = {X, L.S, L.ncw, d.batch, d.C, d.Hp, d.Wp, d.H, d.W, d.ws, *out,
                       prop ? blocks[d.depth - 1].hat_attn.gamma : nullptr, prop ? tables->up_idx : nullptr};
+    if (tail && tail->ln_w) return launch_reverse_ln(rc, tail->ln_w, tail->ln_b, tail->ln_eps, st);
     FVIT_TRY(launch_reverse(rc, st));
     return FVIT_OK;
 }

@@ -499,6 +499,11 @@ struct ReverseCall {
     const int32_t* up_idx; // null => no propagation
 };
 int launch_reverse(const ReverseCall& c, hipStream_t stream);
+// window_reverse with LayerNorm2d over C of the rounded row (16-bit channel-contiguous maps, C <= 512: reverse_ln_supported)
+bool reverse_ln_supported(const ReverseCall& c);
+int launch_reverse_ln(const ReverseCall& c, const float* ln_w, const float* ln_b, float eps, hipStream_t stream);
+// out[b][c] = mean over the `rows` f32 rows of image b of the value rounded through the 16-bit type round_dtype
+int launch_rows_avgpool(const float* x, float* out, int batch, int rows, int C, int round_dtype, hipStream_t stream);
 
 // copy f32 rows [rows][C] out of / into the windowed tensor's carrier slots (block-level API)
 int launch_ct_copy(float* x, int rows_per_win, int row_off, int ncw, float* ct, int nwin_total, int C, int to_x,

@@ -592,6 +592,9 @@ struct HaloParams {
     int tiles_x, tiles_y, tiles;
     int buf_bytes;       // LDS bytes per tile buffer: HALO_BYTES (+ HALO_RES_BYTES with a residual)
     int ablate;          // experiment knob (results are wrong when non-zero): 1 no MFMA loop, 2 no halo/residual DMA, 4 no stores, 8 no epilogue math
+    const float* ln_w;   // LN instance only (fvit_conv3x3_c64_ln2d): LayerNorm2d weight / bias [64] applied to the stored map
+    const float* ln_b;
+    float ln_eps;
 };
 
 constexpr int HALO_TH = 8, HALO_TW = 16, HALO_PW = HALO_TW + 2, HALO_PH = HALO_TH + 2;
@@ -600,14 +603,25 @@ constexpr int HALO_BYTES = HALO_PIECES * 1024;
 constexpr int HALO_RES_BYTES = HALO_TH * HALO_TW * 128;         // the tile's residual pixels, staged next to the halo
 constexpr int HALO_BUF = HALO_BYTES + HALO_RES_BYTES;
 
-template <typename T>
+constexpr int HALO_LN_LDS = 1024 + 2 * HALO_BUF + 1024;        // LN instance: 81 920 B, exactly half a CU's LDS (two workgroups per CU)
+
+// LN (the conv that ends a level: bias + residual epilogue only): the stored map is LayerNorm2d, over the 64 channels of a pixel, of the map the plain
+// instance stores -- statistics in fp32 from the ROUNDED 16-bit values, two passes (mean, then squared deviations), each reduced in-lane (8 channels),
+// across the wave's four 16-lane groups (v_permlane swaps) and across the two `ch` waves of a pixel row group through 1 KiB of LDS: pass 1 in a 1-KiB
+// area behind the tile buffers, pass 2 in the head of the current tile's halo, which no wave reads once all have passed the barrier of pass 1.  pk[]
+// then carries the normalised values through the deferred store.
+template <typename T, bool LN = false>
 __global__ __launch_bounds__(256, 2) void conv3x3_c64_halo_kernel(HaloParams p) {
     typedef typename Op16<T>::v8 v8;
-    // dynamic LDS: [64 floats bias | pad to 1 KiB][2 x (halo + residual tile)]; without a residual the second part of each
-    // buffer is neither allocated nor touched (buffer stride p.buf_bytes)
+    // dynamic LDS: [64 floats bias | LN: 64 weight | 64 bias | pad to 1 KiB][2 x (halo + residual tile)][LN: 1 KiB]; without a residual the second
+    // part of each buffer is neither allocated nor touched (buffer stride p.buf_bytes)
     extern __shared__ __attribute__((aligned(1024))) char smem_dyn[];
     float* sbias = (float*)smem_dyn;
     char* smem = smem_dyn + 1024;
+    if constexpr (LN) {
+        if (threadIdx.x >= 64 && threadIdx.x < 128) sbias[threadIdx.x] = p.ln_w[threadIdx.x - 64];
+        if (threadIdx.x >= 128 && threadIdx.x < 192) sbias[threadIdx.x] = p.ln_b[threadIdx.x - 128];
+    }
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -749,6 +763,66 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_halo_kernel(HaloParams p) 
             bias[0] = t0[0]; bias[1] = t0[1]; bias[2] = t0[2]; bias[3] = t0[3];
             bias[4] = t1[0]; bias[5] = t1[1]; bias[6] = t1[2]; bias[7] = t1[3];
         }
+        if constexpr (LN) {
+            float stat[4];   // pass 1: the wave's channel sum of pixel (4 ph + mi, s); pass 2: its sum of squared deviations
+#pragma unroll
+            for (int mi = 0; mi < 4; ++mi) {
+                const v8 rv = *(const v8*)(tb + roff + mi * (HALO_TW * 128));
+                v8 ov;
+                float sum = 0.f;
+#pragma unroll
+                for (int ni = 0; ni < 2; ++ni) {
+                    const f4 a = acc[ni][mi];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const T o = (T)(a[r] + bias[ni * 4 + r] + (float)rv[ni * 4 + r]);   // the value the plain instance stores
+                        ov[ni * 4 + r] = o;
+                        sum += (float)o;
+                    }
+                }
+                pk[mi] = ov;
+                stat[mi] = sum_xor32(sum_xor16(sum));
+            }
+            float mean[4];
+#pragma unroll
+            for (int pass = 0; pass < 2; ++pass) {
+                // [ch][pixel 16 (4 ph + mi) + s]; pass 2 reuses the head of this tile's halo: every wave is past its MFMA loop after the barrier of pass 1
+                float* red = (float*)(pass == 0 ? smem + 2 * HALO_BUF : smem + cur * HALO_BUF);
+                if (g == 0) {
+#pragma unroll
+                    for (int mi = 0; mi < 4; ++mi) red[ch * 128 + (ph * 4 + mi) * 16 + s] = stat[mi];
+                }
+                asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+#pragma unroll
+                for (int mi = 0; mi < 4; ++mi) {
+                    const float* q = red + (ph * 4 + mi) * 16 + s;
+                    const float tot = q[0] + q[128];   // the same order in both waves
+                    if (pass == 0) {
+                        mean[mi] = tot * (1.f / 64.f);
+                        float sq = 0.f;
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) { const float d = (float)pk[mi][j] - mean[mi]; sq += d * d; }
+                        stat[mi] = sum_xor32(sum_xor16(sq));
+                    } else {
+                        stat[mi] = rsqrtf(tot * (1.f / 64.f) + p.ln_eps);
+                    }
+                }
+            }
+            float lw[8], lb[8];
+            {
+                const f4 w0 = *(const f4*)(sbias + 64 + nb), w1 = *(const f4*)(sbias + 64 + nb + 4);
+                const f4 b0 = *(const f4*)(sbias + 128 + nb), b1 = *(const f4*)(sbias + 128 + nb + 4);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { lw[j] = w0[j]; lw[4 + j] = w1[j]; lb[j] = b0[j]; lb[4 + j] = b1[j]; }
+            }
+#pragma unroll
+            for (int mi = 0; mi < 4; ++mi) {
+                v8 nv;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) nv[j] = (T)(((float)pk[mi][j] - mean[mi]) * stat[mi] * lw[j] + lb[j]);
+                pk[mi] = nv;
+            }
+        } else
         if (!(p.ablate & 8))
             dispatch_epilogue(p.act, R != nullptr, [&](auto act_tag, auto res_tag) {
                 constexpr int ACT = decltype(act_tag)::value;
@@ -787,8 +861,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_halo_kernel(HaloParams p) 
 }
 
 template <typename T>
-int launch_halo_t(const ConvParams& c, hipStream_t stream) {
+int launch_halo_t(const ConvParams& c, hipStream_t stream, const float* ln_w = nullptr, const float* ln_b = nullptr, float ln_eps = 0.f) {
     HaloParams p;
+    p.ln_w = ln_w; p.ln_b = ln_b; p.ln_eps = ln_eps;
     p.in = c.in; p.w = c.w; p.bias = c.bias; p.res = c.res; p.out = c.out; p.zeros = c.zeros;
     p.B = c.B; p.H = c.Hi; p.W = c.Wi; p.act = c.act;
     p.tiles_x = (c.Wi + HALO_TW - 1) / HALO_TW;
@@ -801,8 +876,20 @@ int launch_halo_t(const ConvParams& c, hipStream_t stream) {
     const double flops = 2.0 * c.M * 64.0 * 576.0;
     const double bytes = 2.0 * ((double)c.M * 64 * (c.res ? 3.0 : 2.0) + 576.0 * 64);
     ProfScope prof(FVIT_K_CONV, flops, bytes, stream);
-    prof_note("conv3x3_c64_halo_kernel", grid);
+    prof_note(ln_w ? "conv3x3_c64_halo_kernel<ln>" : "conv3x3_c64_halo_kernel", grid);
     p.buf_bytes = c.res ? HALO_BUF : HALO_BYTES;
+    if (ln_w) {   // the caller checked: residual epilogue, no activation
+        static DeviceOnce once_ln;
+        if (once_ln.first_on_current_device())
+            hipFuncSetAttribute((const void*)conv3x3_c64_halo_kernel<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, HALO_LN_LDS);
+        if (tune_get("conv_halo_debug", 0)) {
+            int nb = -1;
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)conv3x3_c64_halo_kernel<T, true>, 256, HALO_LN_LDS);
+            fprintf(stderr, "[fvit] conv3x3_c64_halo<ln>: grid %d, tiles %d, dynamic LDS %d B, resident workgroups/CU %d\n", grid, p.tiles, HALO_LN_LDS, nb);
+        }
+        hipLaunchKernelGGL((conv3x3_c64_halo_kernel<T, true>), dim3(grid), dim3(256), HALO_LN_LDS, stream, p);
+        return check_launch("conv3x3_c64_halo_kernel<ln>");
+    }
     const size_t lds = 1024 + 2 * (size_t)p.buf_bytes;
     static DeviceOnce once;   // > 64 KiB of dynamic LDS needs the opt-in attribute (once per device and kernel instance)
     if (once.first_on_current_device())
@@ -847,6 +934,9 @@ struct BandParams {
     int PW, R, bands;    // padded row pitch W + 2, output rows per band, bands per image
     int npieces;         // 1-KiB pieces (4 pixels) of the band's (R + 2) x PW halo image
     int magic;           // ceil(65536 / PW): n / PW == (n * magic) >> 16 for n < 2048
+    const float* ln_w;   // LN instance only (fvit_conv3x3_c128_band_ln2d): LayerNorm2d weight / bias [128] applied to the stored map
+    const float* ln_b;
+    float ln_eps;
     unsigned long long* ts;   // TS instance only (fvit_debug_conv_band_timeline): s_memtime stamps [workgroup][wave][8]: 0 start, 1 band DMA and
                               // first weight steps requested, 2 band landed (barrier passed), 3 K loop done, 4 residual rows landed, 5 end
 };
@@ -862,7 +952,10 @@ constexpr int BD_MAXPW = 32;
 constexpr int BD_PIX = (BD_NG * 16 + 2 * BD_MAXPW + 2 + 3) / 4 * 4;   // LDS pixels a read can touch: 292
 constexpr int BD_LDS = BD_PIX * 256;                        // 74 752 B
 
-template <typename T, bool TS = false>
+// LN (the conv that ends a level: bias + residual epilogue only): the stored map is LayerNorm2d, over the 128 channels of a pixel, of the map the plain
+// instance stores -- statistics in fp32 from the ROUNDED 16-bit values, two passes (mean, then squared deviations), each reduced in-lane (8 channels),
+// across the wave's four 16-lane groups (v_permlane swaps) and across the four waves through the band's LDS, which is dead after the K loop.
+template <typename T, bool TS = false, bool LN = false>
 __global__ __launch_bounds__(256, 2) void conv3x3_c128_band_kernel(BandParams p) {
     typedef typename Op16<T>::v8 v8;
 #define FVIT_BD_STAMP(k) if constexpr (TS) { if ((threadIdx.x & 63) == 0) p.ts[((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 8 + (k)] = __builtin_amdgcn_s_memtime(); }
@@ -979,6 +1072,78 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c128_band_kernel(BandParams p)
     }
     T* O = (T*)p.out + (size_t)img * p.H * p.W * 128 + nb;
     const T* Rs = p.res ? (const T*)p.res + (size_t)img * p.H * p.W * 128 + nb : nullptr;
+    if constexpr (LN) {
+        // position q = 16 i + s of the band: its pixel's element offset, or -1 for a pad position / a row below the map
+        auto pix_off = [&](int i) {
+            const int q = i * 16 + s;
+            const int r = (q * p.magic) >> 16, x = q - r * PW, y = y0 + r;
+            return (r < p.R && y < p.H && x < p.W) ? (y * p.W + x) * 128 : -1;
+        };
+        v8 ov[NG];        // the map the plain instance stores
+        float stat[NG];   // pass 1: the wave's channel sum of the pixel; pass 2: its sum of squared deviations
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            v8 rv[HB];
+#pragma unroll
+            for (int i = 0; i < HB; ++i) rv[i] = *(const v8*)(Rs + max(pix_off(h * HB + i), 0));
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int i = 0; i < HB; ++i) {
+                float sum = 0.f;
+#pragma unroll
+                for (int ni = 0; ni < 2; ++ni) {
+                    const f4 a = acc[ni][h * HB + i];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const T o = (T)(a[r] + bias[ni * 4 + r] + (float)rv[i][ni * 4 + r]);
+                        ov[h * HB + i][ni * 4 + r] = o;
+                        sum += (float)o;
+                    }
+                }
+                stat[h * HB + i] = sum_xor32(sum_xor16(sum));
+            }
+        }
+        float* red = (float*)smem;   // [2 passes][4 waves][NG * 16 positions]
+        float mean[NG];
+#pragma unroll
+        for (int pass = 0; pass < 2; ++pass) {
+            float* rp = red + pass * (4 * NG * 16);
+            if (pass == 0) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // every wave has left the K loop: the band image is dead
+            if (g == 0) {
+#pragma unroll
+                for (int i = 0; i < NG; ++i) rp[wave * (NG * 16) + i * 16 + s] = stat[i];
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+#pragma unroll
+            for (int i = 0; i < NG; ++i) {
+                const float* q = rp + i * 16 + s;
+                const float tot = (q[0] + q[NG * 16]) + (q[2 * NG * 16] + q[3 * NG * 16]);   // the same order in every wave
+                if (pass == 0) {
+                    mean[i] = tot * (1.f / 128.f);
+                    float sq = 0.f;
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) { const float d = (float)ov[i][j] - mean[i]; sq += d * d; }
+                    stat[i] = sum_xor32(sum_xor16(sq));
+                } else {
+                    stat[i] = rsqrtf(tot * (1.f / 128.f) + p.ln_eps);
+                }
+            }
+        }
+        float lw[8], lb[8];
+        {
+            const f4 w0 = *(const f4*)(p.ln_w + nb), w1 = *(const f4*)(p.ln_w + nb + 4), b0 = *(const f4*)(p.ln_b + nb), b1 = *(const f4*)(p.ln_b + nb + 4);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { lw[j] = w0[j]; lw[4 + j] = w1[j]; lb[j] = b0[j]; lb[4 + j] = b1[j]; }
+        }
+#pragma unroll
+        for (int i = 0; i < NG; ++i) {
+            v8 nv;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) nv[j] = (T)(((float)ov[i][j] - mean[i]) * stat[i] * lw[j] + lb[j]);
+            const int off = pix_off(i);
+            if (off >= 0) *(v8*)(O + off) = nv;
+        }
+    } else
     dispatch_epilogue(p.act, Rs != nullptr, [&](auto act_tag, auto res_tag) {
         constexpr int ACT = decltype(act_tag)::value;
         constexpr bool RES = decltype(res_tag)::value != 0;
@@ -1026,9 +1191,10 @@ bool band_supported(int H, int W) { return H >= 1 && W >= 1 && W + 2 <= BD_MAXPW
 
 template <typename T>
 int launch_band_t(const void* in, const void* wf, const float* bias, const void* res, void* out, const void* zeros, int B, int H, int W, int act,
-                  hipStream_t stream, void* stamps = nullptr) {
+                  hipStream_t stream, void* stamps = nullptr, const float* ln_w = nullptr, const float* ln_b = nullptr, float ln_eps = 0.f) {
     BandParams p;
     p.in = in; p.wf = wf; p.bias = bias; p.res = res; p.out = out; p.zeros = zeros; p.B = B; p.H = H; p.W = W; p.act = act;
+    p.ln_w = ln_w; p.ln_b = ln_b; p.ln_eps = ln_eps;
     p.PW = W + 2;
     p.R = (BD_NG * 16) / p.PW;
     if (p.R > H) p.R = H;
@@ -1037,8 +1203,12 @@ int launch_band_t(const void* in, const void* wf, const float* bias, const void*
     p.magic = (65536 + p.PW - 1) / p.PW;
     const double M = (double)B * H * W;
     ProfScope prof(FVIT_K_CONV, 2.0 * M * 128.0 * 1152.0, 2.0 * (M * 128 * (res ? 3.0 : 2.0) + 1152.0 * 128), stream);
-    prof_note("conv3x3_c128_band_kernel", B * p.bands);
+    prof_note(ln_w ? "conv3x3_c128_band_kernel<ln>" : "conv3x3_c128_band_kernel", B * p.bands);
     p.ts = (unsigned long long*)stamps;
+    if (ln_w) {   // the caller checked: residual epilogue, no activation
+        hipLaunchKernelGGL((conv3x3_c128_band_kernel<T, false, true>), dim3(B * p.bands), dim3(256), 0, stream, p);
+        return check_launch("conv3x3_c128_band_kernel<ln>");
+    }
     if constexpr (std::is_same<T, _Float16>::value) {
         if (stamps) {
             hipLaunchKernelGGL((conv3x3_c128_band_kernel<T, true>), dim3(B * p.bands), dim3(256), 0, stream, p);
@@ -1751,6 +1921,41 @@ extern "C" int fvit_conv3x3_c128_band(int32_t dtype, const void* in, const void*
     if (dtype == FVIT_F16) return launch_band_t<_Float16>(in, w_frag, bias, residual, out, zeros, B, H, W, act, (hipStream_t)stream);
     if (dtype == FVIT_BF16) return launch_band_t<__bf16>(in, w_frag, bias, residual, out, zeros, B, H, W, act, (hipStream_t)stream);
     set_error("conv3x3_c128_band: dtype %d not supported (16-bit maps only)", dtype);
+    return FVIT_EINVAL;
+}
+
+// The conv that ends a 64-channel level with the following Downsample's LayerNorm2d in its epilogue (conv3x3_c64_halo_kernel<.., LN>):
+// out = LayerNorm2d(round16(conv3x3(in) + bias + residual)) over the 64 channels of a pixel.  weight: [64][3][3][64]; residual may alias out.
+extern "C" int fvit_conv3x3_c64_ln2d(int32_t dtype, const void* in, const void* weight, const float* bias, const void* residual, void* out,
+                                     const float* ln_w, const float* ln_b, float eps, int32_t B, int32_t H, int32_t W, const void* zeros,
+                                     fvit_stream_t stream) {
+    if (!in || !weight || !residual || !out || !ln_w || !ln_b || !zeros || B <= 0 || H <= 0 || W <= 0 || (int64_t)B * H * W * 64 > 0x7fffffff) {
+        set_error("conv3x3_c64_ln2d: unsupported arguments B=%d H=%d W=%d (need a residual and LayerNorm2d parameters)", B, H, W);
+        return FVIT_EINVAL;
+    }
+    if (ablate_skip(64)) return FVIT_OK;
+    ConvParams p;
+    p.in = in; p.w = weight; p.bias = bias; p.res = residual; p.out = out; p.zeros = zeros;
+    p.B = B; p.Hi = p.Ho = H; p.Wi = p.Wo = W; p.Cin = p.Cout = 64; p.stride = 1; p.act = 0; p.M = B * H * W;
+    if (dtype == FVIT_F16) return launch_halo_t<_Float16>(p, (hipStream_t)stream, ln_w, ln_b, eps);
+    if (dtype == FVIT_BF16) return launch_halo_t<__bf16>(p, (hipStream_t)stream, ln_w, ln_b, eps);
+    set_error("conv3x3_c64_ln2d: dtype %d not supported (16-bit maps only)", dtype);
+    return FVIT_EINVAL;
+}
+
+// The conv that ends a level with the following Downsample's LayerNorm2d in its epilogue: out = LayerNorm2d(round16(conv + bias + residual)) over the 128
+// channels of a pixel (conv3x3_c128_band_kernel<.., LN>).  residual may alias out.
+extern "C" int fvit_conv3x3_c128_band_ln2d(int32_t dtype, const void* in, const void* w_frag, const float* bias, const void* residual, void* out,
+                                           const float* ln_w, const float* ln_b, float eps, int32_t B, int32_t H, int32_t W, const void* zeros,
+                                           fvit_stream_t stream) {
+    if (!in || !w_frag || !residual || !out || !ln_w || !ln_b || !zeros || B <= 0 || !band_supported(H, W) || (int64_t)B * H * W * 128 > 0x7fffffff) {
+        set_error("conv3x3_c128_band_ln2d: unsupported arguments B=%d H=%d W=%d (need a residual, LayerNorm2d parameters and W <= %d)", B, H, W, BD_MAXPW - 2);
+        return FVIT_EINVAL;
+    }
+    if (ablate_skip(32)) return FVIT_OK;
+    if (dtype == FVIT_F16) return launch_band_t<_Float16>(in, w_frag, bias, residual, out, zeros, B, H, W, 0, (hipStream_t)stream, nullptr, ln_w, ln_b, eps);
+    if (dtype == FVIT_BF16) return launch_band_t<__bf16>(in, w_frag, bias, residual, out, zeros, B, H, W, 0, (hipStream_t)stream, nullptr, ln_w, ln_b, eps);
+    set_error("conv3x3_c128_band_ln2d: dtype %d not supported (16-bit maps only)", dtype);
     return FVIT_EINVAL;
 }
 

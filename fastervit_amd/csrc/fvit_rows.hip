@@ -222,6 +222,91 @@ __global__ __launch_bounds__(256) void map_rows_cl_kernel(MapParams p) {
     }
 }
 
+// --- window_reverse + LayerNorm2d (the Downsample's norm behind a transformer level): one wave per pixel, lane = 8 channels (C <= 512) ---
+// The row is rounded to the map type first -- the value map_rows_cl_kernel<true> stores -- and normalised over C from those rounded values: fp32
+// statistics, two passes (mean, then squared deviations), wave reductions on the VALU (group_sum).  The result is LayerNorm2d of the map the plain
+// reverse writes, without that map's round trip through HBM.
+template <typename MT>
+__global__ __launch_bounds__(256) void map_rows_ln_cl_kernel(MapParams p, const float* __restrict__ ln_w, const float* __restrict__ ln_b, float eps) {
+    typedef MT m8 __attribute__((ext_vector_type(8)));
+    const int lane = threadIdx.x & 63;
+    const int64_t pix = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (pix >= (int64_t)p.batch * p.H * p.W) return;
+    const int b = (int)(pix / (p.H * p.W));
+    const int rem = (int)(pix - (int64_t)b * p.H * p.W);
+    const int y = rem / p.W, xx = rem - y * p.W;
+    const int64_t trow = token_row(p, b, y, xx);
+    const float* xr = p.x + trow * p.C;
+    MT* mp = (MT*)p.map.data + b * p.map.stride_b + y * p.map.stride_h + xx * p.map.stride_w;
+    const int c = lane * 8;
+    const bool on = c < p.C;
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = 0.f;
+    if (on) {
+        f4 a = *(const f4*)(xr + c), bq = *(const f4*)(xr + c + 4);
+        if (p.up_idx) {
+            const int tok = (int)((trow % p.rows_per_win) - p.row_off);
+            const float* cr = p.x + (trow - (trow % p.rows_per_win) + p.up_idx[tok]) * p.C;
+            const f4 ca = *(const f4*)(cr + c), cb = *(const f4*)(cr + c + 4);
+            const f4 ga = p.gamma ? *(const f4*)(p.gamma + c) : (f4){1.f, 1.f, 1.f, 1.f};
+            const f4 gb = p.gamma ? *(const f4*)(p.gamma + c + 4) : (f4){1.f, 1.f, 1.f, 1.f};
+            a += ga * ca;
+            bq += gb * cb;
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { v[r] = (float)(MT)a[r]; v[4 + r] = (float)(MT)bq[r]; }
+    }
+    float sum = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) sum += v[j];
+    const float mean = group_sum<64>(sum) / (float)p.C;
+    float sq = 0.f;
+    if (on) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { const float d = v[j] - mean; sq += d * d; }
+    }
+    const float rstd = rsqrtf(group_sum<64>(sq) / (float)p.C + eps);
+    if (on) {
+        const f4 w0 = *(const f4*)(ln_w + c), w1 = *(const f4*)(ln_w + c + 4), b0 = *(const f4*)(ln_b + c), b1 = *(const f4*)(ln_b + c + 4);
+        m8 o;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            o[r] = (MT)((v[r] - mean) * rstd * w0[r] + b0[r]);
+            o[4 + r] = (MT)((v[4 + r] - mean) * rstd * w1[r] + b1[r]);
+        }
+        *(m8*)(mp + c) = o;
+    }
+}
+
+// --- global average pool straight from the token rows of a one-window, carrier-free level (the classifier's last level) ---
+// feat[b][c] = mean over the ws * ws rows of image b of round_MT(x[row][c]): what window_reverse into an MT map followed by avgpool_kernel gives.  With one
+// window per image a token's row index IS its pixel index, so the sums run in avgpool_kernel's order (wave w takes rows w, w + 4, ..; a fixed tree over
+// the 4 waves): the same bits.  One workgroup per (256-channel group, image); lane = 4 channels.
+template <typename MT>
+__global__ __launch_bounds__(256) void rows_avgpool_kernel(const float* __restrict__ x, float* __restrict__ out, int rows, int C) {
+    __shared__ f4 part[4][64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int b = blockIdx.y, c = blockIdx.x * 256 + lane * 4;
+    f4 s = (f4){0.f, 0.f, 0.f, 0.f};
+    if (c < C) {
+        const float* src = x + (size_t)b * rows * C + c;
+        for (int r = w; r < rows; r += 4) {
+            const f4 t = *(const f4*)(src + (size_t)r * C);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) s[j] += (float)(MT)t[j];
+        }
+    }
+    part[w][lane] = s;
+    __syncthreads();
+    if (w == 0 && c < C) {
+        f4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = ((part[0][lane][j] + part[1][lane][j]) + (part[2][lane][j] + part[3][lane][j])) / (float)rows;
+        *(f4*)(out + (size_t)b * C + c) = o;
+    }
+}
+
 // --- generic strides (NCHW): 64 pixels x 32 channels tile through LDS ---
 template <bool REVERSE>
 __global__ __launch_bounds__(256) void map_rows_tiled_kernel(MapParams p) {
@@ -489,6 +574,48 @@ int launch_reverse(const ReverseCall& c, hipStream_t stream) {
     const double bytes = (double)c.batch * c.C * c.H * c.W * (elem_size(c.out.dtype) + 4.0);
     ProfScope prof(FVIT_K_REVERSE, 0.0, bytes, stream);
     return launch_map(p, true, stream);
+}
+
+bool reverse_ln_supported(const ReverseCall& c) {
+    const int esz = 2;
+    return (c.out.dtype == FVIT_F16 || c.out.dtype == FVIT_BF16) && c.out.stride_c == 1 && c.C % 8 == 0 && c.C <= 512 && ((uintptr_t)c.out.data % 16) == 0 &&
+           (c.out.stride_b * esz) % 16 == 0 && (c.out.stride_h * esz) % 16 == 0 && (c.out.stride_w * esz) % 16 == 0;
+}
+
+int launch_reverse_ln(const ReverseCall& c, const float* ln_w, const float* ln_b, float eps, hipStream_t stream) {
+    if (c.ws <= 0 || (c.Hp % c.ws) || (c.Wp % c.ws) || c.H > c.Hp || c.W > c.Wp || !ln_w || !ln_b) {
+        set_error("window_reverse_ln: bad geometry Hp=%d Wp=%d H=%d W=%d ws=%d", c.Hp, c.Wp, c.H, c.W, c.ws);
+        return FVIT_EINVAL;
+    }
+    if (!reverse_ln_supported(c)) {
+        set_error("window_reverse_ln: needs a 16-bit channel-contiguous, 16-byte aligned map with C %% 8 == 0 and C <= 512 (C=%d, dtype %d)", c.C, c.out.dtype);
+        return FVIT_EINVAL;
+    }
+    MapParams p;
+    p.map = c.out; p.x = const_cast<float*>(c.x); p.ct = nullptr; p.gamma = c.gamma; p.up_idx = c.up_idx;
+    p.batch = c.batch; p.C = c.C; p.Hp = c.Hp; p.Wp = c.Wp; p.H = c.H; p.W = c.W; p.ws = c.ws;
+    p.rows_per_win = c.rows_per_win; p.row_off = c.row_off; p.ncw = c.row_off;
+    p.nwx = c.Wp / c.ws; p.nw = (c.Hp / c.ws) * p.nwx;
+    const int64_t pix = (int64_t)c.batch * c.H * c.W;
+    const int grid = (int)((pix + 3) / 4);
+    ProfScope prof(FVIT_K_REVERSE, 8.0 * pix * c.C, (double)pix * c.C * (2.0 + 4.0), stream);
+    prof_note("map_rows_ln_cl_kernel", grid);
+    if (c.out.dtype == FVIT_F16) hipLaunchKernelGGL((map_rows_ln_cl_kernel<_Float16>), dim3(grid), dim3(256), 0, stream, p, ln_w, ln_b, eps);
+    else hipLaunchKernelGGL((map_rows_ln_cl_kernel<__bf16>), dim3(grid), dim3(256), 0, stream, p, ln_w, ln_b, eps);
+    return check_launch("window_reverse_ln");
+}
+
+int launch_rows_avgpool(const float* x, float* out, int batch, int rows, int C, int round_dtype, hipStream_t stream) {
+    if (!x || !out || batch <= 0 || rows <= 0 || C <= 0 || (C % 4) || (round_dtype != FVIT_F16 && round_dtype != FVIT_BF16)) {
+        set_error("rows_avgpool: unsupported arguments batch=%d rows=%d C=%d dtype=%d (C %% 4 == 0, a 16-bit map type)", batch, rows, C, round_dtype);
+        return FVIT_EINVAL;
+    }
+    const dim3 grid((C + 255) / 256, batch);
+    ProfScope prof(FVIT_K_OTHER, (double)batch * rows * C, 4.0 * batch * C * (rows + 1.0), stream);
+    prof_note("rows_avgpool_kernel", (int)(grid.x * grid.y));
+    if (round_dtype == FVIT_F16) hipLaunchKernelGGL((rows_avgpool_kernel<_Float16>), grid, dim3(256), 0, stream, x, out, rows, C);
+    else hipLaunchKernelGGL((rows_avgpool_kernel<__bf16>), grid, dim3(256), 0, stream, x, out, rows, C);
+    return check_launch("rows_avgpool_kernel");
 }
 
 int launch_ct_copy(float* x, int rows_per_win, int row_off, int ncw, float* ct, int nwin_total, int C, int to_x,

@@ -744,12 +744,30 @@ def stage_refs(layer, device, batch: int, H: int, W: int, slot: int = 0) -> tupl
     return tables, pack, wsp, tokw
 
 
-def stage_forward(layer, x: torch.Tensor, tokenizer=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+def pool_tail_supported(layer, x: torch.Tensor) -> bool:
+    """``stage_forward(..., pool_out=...)`` applies to this layer on the map x: one window per image and no carrier tokens."""
+    return bool(len(layer.blocks)) and not layer.blocks[0].do_sr_hat and x.shape[2] == x.shape[3] == layer.window_size and x.dtype in (torch.float16, torch.bfloat16)
+
+
+def ln2d_tail_supported(x: torch.Tensor, out: torch.Tensor) -> bool:
+    """``stage_forward(..., out=out, ln2d=...)`` applies: a 16-bit map with contiguous channels, 16-byte aligned pixels, C % 8 == 0 and C <= 512."""
+    C_ = x.shape[1]
+    return (out.dtype in (torch.float16, torch.bfloat16) and C_ % 8 == 0 and C_ <= 512 and out.stride(1) == 1 and out.data_ptr() % 16 == 0
+            and all(out.stride(d) % 8 == 0 for d in (0, 2, 3)))
+
+
+def stage_forward(layer, x: torch.Tensor, tokenizer=None, out: Optional[torch.Tensor] = None, ln2d=None,
+                  pool_out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Transformer branch of FasterViTLayer.forward (AR:848-869) minus the Downsample.  ``x`` and the optional preallocated
     ``out`` (same shape and dtype) may be arbitrary strided views, e.g. the leading channels of a channel-padded map.
 
     ``tokenizer`` (optional) replaces the layer's TokenInitializer module with an equivalent callable
-    returning f32 (B, G, C) carrier tokens (deploy mode passes a 16-bit channels_last version)."""
+    returning f32 (B, G, C) carrier tokens (deploy mode passes a 16-bit channels_last version).
+
+    The deploy plan's fused tails (``FvitStageTail``), each in place of the window_reverse pass:
+    ``ln2d`` = (weight, bias, eps), fp32 [C]: ``out`` receives LayerNorm2d of the map the stage would have written (``ln2d_tail_supported``);
+    ``pool_out`` = fp32 (B, C): the global average pool of that map is written there, no map is produced and ``pool_out`` is returned
+    (``pool_tail_supported``)."""
     _require_gpu(x, "FasterViTLayer")
     _check_mode(layer, x, "FasterViTLayer")
     if len(layer.blocks) == 0:
@@ -772,18 +790,32 @@ def stage_forward(layer, x: torch.Tensor, tokenizer=None, out: Optional[torch.Te
         with st.lock:
             st, tb, ctables, dc = _prepare(layer, x.device, Hp, Wp)
             wsp = _workspace(st, dc, B, H, W, x.device, bounded=bool(getattr(layer, "dynamic_grid", False)))
-            if out is None:
+            tail = None
+            if pool_out is not None:
+                if ln2d is not None or not pool_tail_supported(layer, x) or tuple(pool_out.shape) != (B, Cc) or pool_out.dtype != torch.float32 \
+                        or not pool_out.is_contiguous() or pool_out.device != x.device:
+                    raise RuntimeError("stage_forward: pool_out needs a contiguous fp32 (B, C) tensor, a 16-bit map of one window per image without "
+                                       "carrier tokens, and excludes ln2d")
+                tail = _lib.FvitStageTail(None, None, pool_out.data_ptr(), 0.0, _DT[x.dtype])
+            elif out is None:
                 out = torch.empty_like(x)  # keeps dtype and memory format (NCHW or channels_last)
             elif out.shape != x.shape or out.dtype != x.dtype or out.device != x.device:
                 raise RuntimeError(f"stage_forward: out {tuple(out.shape)} {out.dtype} does not match x {tuple(x.shape)} {x.dtype}")
-            vin, vout = _map_view(xp), _map_view(out)
+            if ln2d is not None:
+                ln_w, ln_b, eps = ln2d
+                if not ln2d_tail_supported(x, out) or any(t.dtype != torch.float32 or t.numel() < Cc or not t.is_contiguous() or t.device != x.device
+                                                          for t in (ln_w, ln_b)):
+                    raise RuntimeError("stage_forward: ln2d needs fp32 [C] parameters and a 16-bit channel-contiguous out with C % 8 == 0, C <= 512")
+                tail = _lib.FvitStageTail(ln_w.data_ptr(), ln_b.data_ptr(), None, float(eps), 0)
+            vin = _map_view(xp)
+            vout = _map_view(out) if pool_out is None else None
             stream = _acquire(wsp, x.device)
-            rc = lib.fvit_hat_stage_forward(C.byref(wsp.desc), st.blocks_c, C.byref(ctables), C.byref(vin),
-                                            ct.data_ptr() if ct is not None else None, C.byref(vout), wsp.buf.data_ptr(),
-                                            wsp.buf.numel(), stream)
+            rc = lib.fvit_hat_stage_forward_tail(C.byref(wsp.desc), st.blocks_c, C.byref(ctables), C.byref(vin),
+                                                 ct.data_ptr() if ct is not None else None, C.byref(vout) if vout is not None else None,
+                                                 C.byref(tail) if tail is not None else None, wsp.buf.data_ptr(), wsp.buf.numel(), stream)
             _lib.check(rc, "fvit_hat_stage_forward")
             _release(wsp, x.device)
-        return out
+        return out if pool_out is None else pool_out
 
 
 def block_forward(blk, x: torch.Tensor, carrier_tokens: Optional[torch.Tensor]):

@@ -194,6 +194,26 @@ int fvit_hat_stage_forward(const FvitStageDesc* desc, const FvitBlockWeights* bl
                            const float* ct_init, const FvitMapView* out, void* workspace,
                            size_t workspace_bytes, fvit_stream_t stream);
 
+/* The same stage with its window_reverse replaced by a fused tail (NULL tail or an all-zero one = fvit_hat_stage_forward):
+ *   ln_w / ln_b : f32 [C] LayerNorm2d parameters (the following Downsample's norm): out = LayerNorm2d over C of the 16-bit map the plain reverse
+ *                 writes, statistics taken from the rounded values.  16-bit channel-contiguous, 16-byte aligned out with C % 8 == 0, C <= 512.
+ *   pool_out    : f32 [B][C]: no reverse and no map (out may be NULL): the mean over the image's tokens of each value rounded through pool_dtype
+ *                 (FVIT_F16 / FVIT_BF16), i.e. AdaptiveAvgPool2d(1) of the map the plain reverse writes in that type.  One window per image, no
+ *                 carrier tokens (hier == 0, H == Hp == W == Wp == ws).  Excludes ln_w / ln_b. */
+typedef struct FvitStageTail {
+    const float* ln_w;
+    const float* ln_b;
+    float* pool_out;
+    float ln_eps;
+    int32_t pool_dtype;
+} FvitStageTail;
+int fvit_hat_stage_forward_tail(const FvitStageDesc* desc, const FvitBlockWeights* blocks,
+                                const FvitStageTables* tables, const FvitMapView* in,
+                                const float* ct_init, const FvitMapView* out, const FvitStageTail* tail,
+                                void* workspace, size_t workspace_bytes, fvit_stream_t stream);
+/* The pool of that tail on its own: out[b][c] = mean over the `rows` f32 rows x[b][r][c] of the value rounded through round_dtype (C % 4 == 0). */
+int fvit_rows_avgpool(int32_t round_dtype, const float* x, float* out, int32_t B, int32_t rows, int32_t C, fvit_stream_t stream);
+
 /* HAT.forward on already-partitioned windows (AR:668-707), for callers that drive blocks
  * themselves: x f32 (B*nW, ws^2, C) in/out, ct f32 (B, G, C) in/out (NULL when hier == 0).
  * desc->depth is ignored (one block). */
@@ -533,6 +553,19 @@ int fvit_stem_conv3x3s2_px(int32_t dtype, const FvitMapView* in, const void* wei
 int fvit_conv3x3_c128_band_supported(int32_t H, int32_t W);
 int fvit_conv3x3_c128_band(int32_t dtype, const void* in, const void* w_frag, const float* bias, const void* residual, void* out,
                            int32_t B, int32_t H, int32_t W, int32_t act, const void* zeros, fvit_stream_t stream);
+
+/* The conv that ends a ConvBlock level with the following Downsample's LayerNorm2d (timm, over the channels of a pixel) in its epilogue:
+ *     out = LayerNorm2d(round16(conv3x3(in) + bias + residual)) * ln_w + ln_b
+ * i.e. LayerNorm2d of exactly the 16-bit map the plain kernel stores (statistics in fp32 from the rounded values, two passes), without that map's
+ * round trip through HBM.  Stride 1, no activation, residual required (it may alias out); ln_w / ln_b f32 [C].
+ *   fvit_conv3x3_c64_ln2d       Cin = Cout = 64, weight [64][3][3][64] (the register-stationary halo kernel of fvit_conv3x3_nhwc)
+ *   fvit_conv3x3_c128_band_ln2d Cin = Cout = 128, w_frag and the W <= 30 limit of fvit_conv3x3_c128_band */
+int fvit_conv3x3_c64_ln2d(int32_t dtype, const void* in, const void* weight, const float* bias, const void* residual, void* out,
+                          const float* ln_w, const float* ln_b, float eps, int32_t B, int32_t H, int32_t W, const void* zeros,
+                          fvit_stream_t stream);
+int fvit_conv3x3_c128_band_ln2d(int32_t dtype, const void* in, const void* w_frag, const float* bias, const void* residual, void* out,
+                                const float* ln_w, const float* ln_b, float eps, int32_t B, int32_t H, int32_t W, const void* zeros,
+                                fvit_stream_t stream);
 
 /* Stem convolution of PatchEmbed (FV:458-460): 3x3, stride 2, pad 1, 3 -> 64 channels, + bias (folded BatchNorm) + ReLU.
  * in: strided view of the (B, 3, Hi, Wi) image in fp32 / fp16 / bf16 (the model's NCHW fp32 input needs no conversion);
