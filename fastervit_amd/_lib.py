@@ -41,6 +41,7 @@ EXPORTED_SYMBOLS = (
     "fvit_bwd_window_attention_long_workspace", "fvit_tune", "fvit_prof_enable", "fvit_prof_collect",
     "fvit_prof_records", "fvit_prof_kind_name",
     "fvit_hat_stage_forward_tail", "fvit_rows_avgpool", "fvit_conv3x3_c64_ln2d", "fvit_conv3x3_c128_band_ln2d",
+    "fvit_conv3x3", "fvit_conv3x3_route", "fvit_conv3x3_route_name",
 )
 # only in libfvit_hip_diag.so (the same sources with -DFVIT_DIAG; FVIT_DIAG=1 selects it): diagnosis entry points of include/fvit_hip.h's #ifdef FVIT_DIAG
 # section.  The shipped library exports none of them and compiles the ablation knobs out (tests/test_abi.py).
@@ -91,6 +92,15 @@ class FvitMapView(C.Structure):
                 ("stride_w", C.c_int64), ("dtype", C.c_int32), ("_pad", C.c_int32)]
 
 
+class FvitConvWeights(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("classic", "dense", "band_frag")] + [("terms", C.c_int32), ("cin_valid", C.c_int32)]
+
+
+class FvitConvCall(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("in_", "in_lo", "bias", "residual", "residual_lo", "out", "out_lo", "out_f32", "ln_w", "ln_b", "zeros")] + \
+               [("ln_eps", C.c_float)] + [(n, C.c_int32) for n in ("B", "Hi", "Wi", "Cin", "Cout", "stride", "act", "px")]
+
+
 class FvitProfEntry(C.Structure):
     _fields_ = [("launches", C.c_int64), ("ms", C.c_double), ("flops", C.c_double), ("bytes", C.c_double)]
 
@@ -137,6 +147,12 @@ def _declare(lib):
     for fn in (lib.fvit_conv3x3_c64_ln2d, lib.fvit_conv3x3_c128_band_ln2d):
         fn.restype = C.c_int
         fn.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, f32, i32, i32, i32, vp, vp]
+    lib.fvit_conv3x3.restype = C.c_int
+    lib.fvit_conv3x3.argtypes = [i32, C.POINTER(FvitConvWeights), C.POINTER(FvitConvCall), vp]
+    lib.fvit_conv3x3_route.restype = C.c_int
+    lib.fvit_conv3x3_route.argtypes = [i32, C.POINTER(FvitConvWeights), C.POINTER(FvitConvCall)]
+    lib.fvit_conv3x3_route_name.restype = C.c_char_p
+    lib.fvit_conv3x3_route_name.argtypes = [C.c_int]
     lib.fvit_hat_block_forward.restype = C.c_int
     lib.fvit_hat_block_forward.argtypes = [C.POINTER(FvitStageDesc), C.POINTER(FvitBlockWeights),
                                            C.POINTER(FvitStageTables), vp, vp, vp, C.c_size_t, vp]

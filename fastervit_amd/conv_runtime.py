@@ -54,6 +54,10 @@ def _stream(device=None):
     return torch.cuda.current_stream(device).cuda_stream
 
 
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
 def _bn_scale_shift(bn):
     s = bn.weight.float() / torch.sqrt(bn.running_var.float() + bn.eps)
     t = bn.bias.float() - bn.running_mean.float() * s
@@ -73,7 +77,7 @@ def _fold(conv, bn, extra_scale=None):
 
 def frag_pack_conv128(w2d: torch.Tensor) -> torch.Tensor:
     """[128][9 * 128] conv weight (row = output channel, column k = tap * 128 + input channel) -> the fragment-order stream of
-    fvit_conv3x3_c128_band (include/fvit_hip.h): [wave 4][step 36][ni 2][lane 64][8]; element e of lane 16 g + s of fragment
+    row-band conv kernel (FvitConvWeights.band_frag, include/fvit_hip.h): [wave 4][step 36][ni 2][lane 64][8]; element e of lane 16 g + s of fragment
     (wave, step, ni) = w2d[32 wave + (s >> 2) * 8 + ni * 4 + (s & 3)][step * 32 + 8 g + e]."""
     assert tuple(w2d.shape) == (128, 1152)
     dev = w2d.device
@@ -93,6 +97,11 @@ class ConvWeight(NamedTuple):
     terms: int                           # weight terms in wk (2 = hi | lo)
     cv: int                              # channels wk contracts over per tap
     wk_classic: Optional[torch.Tensor]   # beside a dense-K wk: the classic rows, which the patch form of the kernel takes
+
+    def images(self) -> _lib.FvitConvWeights:
+        """Every packed image for the conv driver (``fvit_conv3x3``): ``wk`` is the dense image when ``wk_classic`` is set, the classic one otherwise."""
+        classic, dense = (self.wk, None) if self.wk_classic is None else (self.wk_classic, self.wk)
+        return _lib.FvitConvWeights(_ptr(classic), _ptr(dense), _ptr(self.wband), self.terms, self.cv)
 
 
 # the entries of ``DeployPlan.t`` (``_build``); biases and LayerNorm2d parameters are fp32, zero-padded to the map layout
@@ -191,21 +200,21 @@ class DeployPlan:
             lo = (w - wcl.float()).to(self.dtype).permute(0, 2, 3, 1).contiguous() if terms == 2 else None
             cv8 = (ci0 + 7) // 8 * 8
             if self.dense_k and cv8 < ci:
-                # r06: the pad channels of the INPUT map leave the contraction (fvit_conv3x3_nhwc_dense): [Cout][terms][kd], column t * cv + c
+                # r06: the pad channels of the INPUT map leave the contraction (dense K, include/fvit_hip.h): [Cout][terms][kd], column t * cv + c
                 cv, kd = cv8, (9 * cv8 + 63) // 64 * 64
 
                 def dense(m):   # m: (co, 3, 3, ci)
                     d = torch.zeros((co, kd), dtype=m.dtype, device=m.device)
                     d[:, :9 * cv] = m[..., :cv].reshape(co, 9 * cv)
                     return d
-                # (the classic matrix next to the dense one: the patch form of the kernel -- fvit_conv3x3_patch_form, chosen per call from the map size -- takes it)
+                # (the classic matrix next to the dense one: the patch form of the kernel, which the driver chooses per call from the map size, takes it)
                 classic = wk.reshape(co, -1) if lo is None else torch.cat([wk.reshape(co, -1), lo.reshape(co, -1)], dim=1).contiguous()
                 wk = dense(wk) if lo is None else torch.cat([dense(wk), dense(lo)], dim=1).contiguous()
                 return ConvWeight(wcl, wk, None, terms, cv, classic)
-            if terms == 2:   # [Cout][hi (3,3,Cin) | lo (3,3,Cin)]: fvit_conv3x3_nhwc_terms
+            if terms == 2:   # [Cout][hi (3,3,Cin) | lo (3,3,Cin)]
                 wk = torch.cat([wk.reshape(co, -1), lo.reshape(co, -1)], dim=1).contiguous()
                 return ConvWeight(wcl, wk, None, 2, cv, None)
-            if (co, ci) == (128, 128):   # the fragment-order image fvit_conv3x3_c128_band streams (level 1 of FasterViT-0)
+            if (co, ci) == (128, 128):   # the fragment-order image the row-band kernel streams (level 1 of FasterViT-0)
                 wband = frag_pack_conv128(wk.reshape(128, 1152))
         return ConvWeight(wcl, wk, wband, 1, cv, None)
 
@@ -216,56 +225,29 @@ class DeployPlan:
             self.zeros = torch.zeros(256, dtype=self.dtype, device=device)
         return self.zeros.data_ptr()
 
-    @staticmethod
-    def _conv_launch_shape(x, w: ConvWeight, stride):
-        """(weight rows, cv, Co, Ho, Wo) of one implicit-GEMM launch on the map x."""
+    def _launch_conv(self, x, w: ConvWeight, bias, stride, act, x_lo=None, res=None, res_lo=None, out=None, out_lo=None, out_f32=None, px=False,
+                     ln: Optional["DownW"] = None):
+        """One ``fvit_conv3x3`` launch on the channels_last map x: the driver picks the kernel from the shape and the images of ``w``.  ``ln``: a
+        Downsample whose LayerNorm2d the conv should apply in its epilogue -- the driver is asked for its route first, a route without that epilogue
+        runs the plain conv.  Returns whether the LayerNorm2d was applied."""
         B, Ci, Hi, Wi = x.shape
-        wk, cv, Co = w.wk, w.cv, w.wk.shape[0]
-        if w.wk_classic is not None and _lib.lib().fvit_conv3x3_patch_form(B, Hi, Wi, Ci, Co, stride):
-            wk, cv = w.wk_classic, Ci   # 8 x 16 patches + halo tiles (r06): the classic [Cout][terms][3][3][Cin] rows
-        return wk, cv, Co, (Hi - 1) // stride + 1, (Wi - 1) // stride + 1
-
-    def _conv_ln2d_route(self, x, w: ConvWeight, d: "DownW"):
-        """Which kernel runs a level's last residual conv on the map x WITH the Downsample's LayerNorm2d in its epilogue: 'halo' (64 channels), 'band'
-        (128 channels, maps the row-band kernel takes), or None = the conv and the LayerNorm2d pass apart."""
-        C_ = x.shape[1]
-        if self.precise or not self.use_hip_conv or not self.fuse_conv_ln2d.get(C_, False) or d.cin != C_ or w.wk is None or w.terms != 1 \
-                or w.wk_classic is not None or not x.is_contiguous(memory_format=torch.channels_last):
-            return None
-        lib = _lib.lib()
-        if C_ == 64 and tuple(w.wk.shape) == (64, 3, 3, 64):
-            return "halo"
-        if C_ == 128 and w.wband is not None and lib.fvit_conv3x3_c128_band_supported(x.shape[2], x.shape[3]):
-            return "band"
-        return None
-
-    def _conv_ln2d(self, route, x, w: ConvWeight, bias, residual, d: "DownW"):
-        """LayerNorm2d(conv3x3(x, w) + bias + residual), in place on the residual: one kernel (``_conv_ln2d_route``)."""
-        B, _, Hi, Wi = x.shape
-        fn, wt, name = ((_lib.lib().fvit_conv3x3_c64_ln2d, w.wk, "fvit_conv3x3_c64_ln2d") if route == "halo" else
-                        (_lib.lib().fvit_conv3x3_c128_band_ln2d, w.wband, "fvit_conv3x3_c128_band_ln2d"))
-        _lib.check(fn(self.code, x.data_ptr(), wt.data_ptr(), bias.data_ptr() if bias is not None else None, residual.data_ptr(), residual.data_ptr(),
-                      d.ln_w.data_ptr(), d.ln_b.data_ptr(), d.eps, B, Hi, Wi, self._zero_page(x.device), _stream(self.dev)), name)
-        return residual
+        lib, wts = _lib.lib(), w.images()
+        call = _lib.FvitConvCall(x.data_ptr(), _ptr(x_lo), _ptr(bias), _ptr(res), _ptr(res_lo), _ptr(out), _ptr(out_lo), _ptr(out_f32), None, None,
+                                 self._zero_page(x.device), 0.0, B, Hi, Wi, Ci, w.wk.shape[0], stride, act, int(px))
+        if ln is not None:
+            call.ln_w, call.ln_b, call.ln_eps = ln.ln_w.data_ptr(), ln.ln_b.data_ptr(), ln.eps
+            if not lib.fvit_conv3x3_route_name(lib.fvit_conv3x3_route(self.code, wts, call)).endswith(b"<ln>"):
+                call.ln_w = call.ln_b = ln = None
+        _lib.check(lib.fvit_conv3x3(self.code, wts, call, _stream(self.dev)), "fvit_conv3x3")
+        return ln is not None
 
     def _conv(self, x, w: ConvWeight, bias, stride, act, residual=None):
         """act(conv3x3(x, w) + bias) (+ residual): one fused HIP kernel when supported, else MIOpen conv + glue passes."""
         B, Ci, Hi, Wi = x.shape
         if w.wk is not None and x.is_contiguous(memory_format=torch.channels_last):
-            wk, cv, Co, Ho, Wo = self._conv_launch_shape(x, w, stride)
-            out = residual if residual is not None else torch.empty((B, Co, Ho, Wo), dtype=self.dtype, device=x.device,
-                                                                    memory_format=torch.channels_last)
-            zeros = self._zero_page(x.device)
-            if w.wband is not None and stride == 1 and _lib.lib().fvit_conv3x3_c128_band_supported(Hi, Wi):   # level 1 of FasterViT-0: one row band of an image per workgroup, weights streamed in fragment order
-                rc = _lib.lib().fvit_conv3x3_c128_band(self.code, x.data_ptr(), w.wband.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                                       residual.data_ptr() if residual is not None else None, out.data_ptr(), B, Hi, Wi, act,
-                                                       zeros, _stream(self.dev))
-                _lib.check(rc, "fvit_conv3x3_c128_band")
-                return out
-            rc = _lib.lib().fvit_conv3x3_nhwc_dense(self.code, x.data_ptr(), wk.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                                    residual.data_ptr() if residual is not None else None, out.data_ptr(), B, Hi, Wi,
-                                                    Ci, cv, Co, stride, act, w.terms, zeros, _stream(self.dev))
-            _lib.check(rc, "fvit_conv3x3_nhwc_dense")
+            out = residual if residual is not None else torch.empty((B, w.wk.shape[0], (Hi - 1) // stride + 1, (Wi - 1) // stride + 1), dtype=self.dtype,
+                                                                    device=x.device, memory_format=torch.channels_last)
+            self._launch_conv(x, w, bias, stride, act, res=residual, out=out)
             return out
         y = F.conv2d(x, w.wcl, None, stride, 1)
         if residual is not None:
@@ -485,21 +467,15 @@ class DeployPlan:
         if w.wk is None or not x.is_contiguous(memory_format=torch.channels_last):
             raise RuntimeError("precise deploy plan: this conv shape has no implicit-GEMM kernel (channel counts must pad to multiples of 64)")
         B, Ci, Hi, Wi = x.shape
-        wk, cv, Co, Ho, Wo = self._conv_launch_shape(x, w, stride)
-        zeros = self._zero_page(x.device)
+        shape = (B, w.wk.shape[0], (Hi - 1) // stride + 1, (Wi - 1) // stride + 1)
         hi = lo = f32 = None
         if want == "f32":
-            f32 = torch.empty((B, Co, Ho, Wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+            f32 = torch.empty(shape, dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
         else:
-            hi = res if res is not None else torch.empty((B, Co, Ho, Wo), dtype=self.dtype, device=x.device, memory_format=torch.channels_last)
+            hi = res if res is not None else torch.empty(shape, dtype=self.dtype, device=x.device, memory_format=torch.channels_last)
             if want == "planes":
                 lo = res_lo if res_lo is not None else torch.empty_like(hi)
-        rc = _lib.lib().fvit_conv3x3_nhwc_px_dense(self.code, x.data_ptr(), x_lo.data_ptr() if x_lo is not None else None, wk.data_ptr(),
-                                             bias.data_ptr() if bias is not None else None, res.data_ptr() if res is not None else None,
-                                             res_lo.data_ptr() if res_lo is not None else None, hi.data_ptr() if hi is not None else None,
-                                             lo.data_ptr() if lo is not None else None, f32.data_ptr() if f32 is not None else None,
-                                             B, Hi, Wi, Ci, cv, Co, stride, act, w.terms, zeros, _stream(self.dev))
-        _lib.check(rc, "fvit_conv3x3_nhwc_px_dense")
+        self._launch_conv(x, w, bias, stride, act, x_lo=x_lo, res=res, res_lo=res_lo, out=hi, out_lo=lo, out_f32=f32, px=True)
         return f32 if want == "f32" else (hi, lo)
 
     def _ln2d_px(self, x, x_lo, x_f32, w, b, eps, c_valid):
@@ -581,15 +557,16 @@ class DeployPlan:
         return self._conv(self._conv(x, st.conv0, st.bias0, 2, 1), st.conv1, st.bias1, 2, 1)
 
     def _conv_level(self, x, blocks, down: Optional["DownW"] = None):
-        """The ConvBlocks of a level, in place on the stream -> (map, normed).  ``down``: the following Downsample; where the last conv's kernel can
-        (``_conv_ln2d_route``) it applies that Downsample's LayerNorm2d in its epilogue and ``normed`` is True."""
+        """The ConvBlocks of a level, in place on the stream -> (map, normed).  ``down``: the following Downsample; where the plan wants it (16-bit plan,
+        ``fuse_conv_ln2d``, an unpadded map) and the last conv's kernel can (``_launch_conv``), that conv applies the Downsample's LayerNorm2d in its
+        epilogue and ``normed`` is True."""
         if not self.precise:
             normed = False
             for i, b in enumerate(blocks):
                 y = self._conv(x, b.conv1, b.bias1, 1, 2)
-                route = self._conv_ln2d_route(y, b.conv2, down) if (down is not None and i + 1 == len(blocks)) else None
-                if route is not None:
-                    x, normed = self._conv_ln2d(route, y, b.conv2, b.bias2, x, down), True
+                if (down is not None and i + 1 == len(blocks) and self.use_hip_conv and self.fuse_conv_ln2d.get(y.shape[1], False) and down.cin == y.shape[1]
+                        and b.conv2.wk is not None and y.is_contiguous(memory_format=torch.channels_last)):
+                    normed = self._launch_conv(y, b.conv2, b.bias2, 1, 0, res=x, out=x, ln=down)
                 else:
                     x = self._conv(y, b.conv2, b.bias2, 1, 0, residual=x)
             return x, normed

@@ -860,49 +860,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_halo_kernel(HaloParams p) 
     if (ptile >= 0) flush(ptile);
 }
 
-template <typename T>
-int launch_halo_t(const ConvParams& c, hipStream_t stream, const float* ln_w = nullptr, const float* ln_b = nullptr, float ln_eps = 0.f) {
-    HaloParams p;
-    p.ln_w = ln_w; p.ln_b = ln_b; p.ln_eps = ln_eps;
-    p.in = c.in; p.w = c.w; p.bias = c.bias; p.res = c.res; p.out = c.out; p.zeros = c.zeros;
-    p.B = c.B; p.H = c.Hi; p.W = c.Wi; p.act = c.act;
-    p.tiles_x = (c.Wi + HALO_TW - 1) / HALO_TW;
-    p.tiles_y = (c.Hi + HALO_TH - 1) / HALO_TH;
-    p.tiles = c.B * p.tiles_x * p.tiles_y;   // <= M, which the caller checked against int32
-    p.ablate = diag_knob("conv_halo_ablate");
-    int maxgrid = tune_get("conv_halo_grid", 512);   // 2 workgroups per CU (230 VGPRs, 46 KiB LDS each)
-    if (maxgrid < 8) maxgrid = 8;                    // every XCD's tile range needs at least one workgroup
-    const int grid = p.tiles < maxgrid ? p.tiles : maxgrid;
-    const double flops = 2.0 * c.M * 64.0 * 576.0;
-    const double bytes = 2.0 * ((double)c.M * 64 * (c.res ? 3.0 : 2.0) + 576.0 * 64);
-    ProfScope prof(FVIT_K_CONV, flops, bytes, stream);
-    prof_note(ln_w ? "conv3x3_c64_halo_kernel<ln>" : "conv3x3_c64_halo_kernel", grid);
-    p.buf_bytes = c.res ? HALO_BUF : HALO_BYTES;
-    if (ln_w) {   // the caller checked: residual epilogue, no activation
-        static DeviceOnce once_ln;
-        if (once_ln.first_on_current_device())
-            hipFuncSetAttribute((const void*)conv3x3_c64_halo_kernel<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, HALO_LN_LDS);
-        if (tune_get("conv_halo_debug", 0)) {
-            int nb = -1;
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)conv3x3_c64_halo_kernel<T, true>, 256, HALO_LN_LDS);
-            fprintf(stderr, "[fvit] conv3x3_c64_halo<ln>: grid %d, tiles %d, dynamic LDS %d B, resident workgroups/CU %d\n", grid, p.tiles, HALO_LN_LDS, nb);
-        }
-        hipLaunchKernelGGL((conv3x3_c64_halo_kernel<T, true>), dim3(grid), dim3(256), HALO_LN_LDS, stream, p);
-        return check_launch("conv3x3_c64_halo_kernel<ln>");
-    }
-    const size_t lds = 1024 + 2 * (size_t)p.buf_bytes;
-    static DeviceOnce once;   // > 64 KiB of dynamic LDS needs the opt-in attribute (once per device and kernel instance)
-    if (once.first_on_current_device())
-        hipFuncSetAttribute((const void*)conv3x3_c64_halo_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, 1024 + 2 * HALO_BUF);
-    if (tune_get("conv_halo_debug", 0)) {
-        int nb = -1;
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)conv3x3_c64_halo_kernel<T>, 256, lds);
-        fprintf(stderr, "[fvit] conv3x3_c64_halo: grid %d, tiles %d, dynamic LDS %zu B, resident workgroups/CU %d\n", grid, p.tiles, lds, nb);
-    }
-    hipLaunchKernelGGL((conv3x3_c64_halo_kernel<T>), dim3(grid), dim3(256), lds, stream, p);
-    return check_launch("conv3x3_c64_halo_kernel");
-}
-
 
 // ------------------------------------------------------------------------------------------------------------
 // Row-band 3x3 convolution for Cin = Cout = 128, stride 1, maps up to 30 pixels wide (ConvBlock convs of level 1 of FasterViT-0:
@@ -1188,36 +1145,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c128_band_kernel(BandParams p)
 }
 
 bool band_supported(int H, int W) { return H >= 1 && W >= 1 && W + 2 <= BD_MAXPW; }
-
-template <typename T>
-int launch_band_t(const void* in, const void* wf, const float* bias, const void* res, void* out, const void* zeros, int B, int H, int W, int act,
-                  hipStream_t stream, void* stamps = nullptr, const float* ln_w = nullptr, const float* ln_b = nullptr, float ln_eps = 0.f) {
-    BandParams p;
-    p.in = in; p.wf = wf; p.bias = bias; p.res = res; p.out = out; p.zeros = zeros; p.B = B; p.H = H; p.W = W; p.act = act;
-    p.ln_w = ln_w; p.ln_b = ln_b; p.ln_eps = ln_eps;
-    p.PW = W + 2;
-    p.R = (BD_NG * 16) / p.PW;
-    if (p.R > H) p.R = H;
-    p.bands = (H + p.R - 1) / p.R;
-    p.npieces = ((p.R + 2) * p.PW + 3) / 4;
-    p.magic = (65536 + p.PW - 1) / p.PW;
-    const double M = (double)B * H * W;
-    ProfScope prof(FVIT_K_CONV, 2.0 * M * 128.0 * 1152.0, 2.0 * (M * 128 * (res ? 3.0 : 2.0) + 1152.0 * 128), stream);
-    prof_note(ln_w ? "conv3x3_c128_band_kernel<ln>" : "conv3x3_c128_band_kernel", B * p.bands);
-    p.ts = (unsigned long long*)stamps;
-    if (ln_w) {   // the caller checked: residual epilogue, no activation
-        hipLaunchKernelGGL((conv3x3_c128_band_kernel<T, false, true>), dim3(B * p.bands), dim3(256), 0, stream, p);
-        return check_launch("conv3x3_c128_band_kernel<ln>");
-    }
-    if constexpr (std::is_same<T, _Float16>::value) {
-        if (stamps) {
-            hipLaunchKernelGGL((conv3x3_c128_band_kernel<T, true>), dim3(B * p.bands), dim3(256), 0, stream, p);
-            return check_launch("conv3x3_c128_band_kernel");
-        }
-    }
-    hipLaunchKernelGGL((conv3x3_c128_band_kernel<T>), dim3(B * p.bands), dim3(256), 0, stream, p);
-    return check_launch("conv3x3_c128_band_kernel");
-}
 
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1572,86 +1499,255 @@ __global__ __launch_bounds__(256, 2) void stem_fused_kernel(StemFusedParams p) {
 #undef FVIT_SF_MARK
 }
 
-// the patch / halo form of the implicit GEMM (conv3x3_kernel<.., HALO>) applies to this launch
-static bool patch_form_ok(const ConvParams& p) {
-    if (!tune_get("conv_patch", 1) || p.stride != 1 || p.cv || p.Cout < 128 || (p.Cin % BK)) return false;
-    if ((int64_t)p.B * p.Hi * p.Wi * p.Cin >= 0x7fffffffLL) return false;   // 32-bit element offsets of the halo rows
-    const int64_t tiles = (int64_t)p.B * ((p.Ho + PATCH_H - 1) / PATCH_H) * ((p.Wo + PATCH_W - 1) / PATCH_W);
-    return tiles * 128 * 100 <= (int64_t)p.M * (100 + tune_get("conv_patch_max_waste_pct", 10));
+// ------------------------------------------------------------------------------------------------------------
+// The conv driver.  choose_conv_route is the only place that asks which kernel runs a 3x3 conv and the only reader of the route knobs;
+// run_conv executes the answer and holds the only launch code.  Every entry point below fills a FvitConvWeights / FvitConvCall for it.
+// ------------------------------------------------------------------------------------------------------------
+enum ConvRoute : int {
+    CR_NONE = -1,
+    CR_HALO64, CR_HALO64_LN,       // conv3x3_c64_halo_kernel: 64 -> 64 channels, stride 1, classic single-term rows
+    CR_BAND128, CR_BAND128_LN,     // conv3x3_c128_band_kernel: 128 -> 128 channels, stride 1, maps up to 30 wide, the fragment stream
+    CR_PATCH, CR_PATCH_PX,         // conv3x3_kernel<.., HALO>: 8 x 16 output patches, classic rows
+    CR_T128, CR_T128_DENSE, CR_T128_PX, CR_T128_PX_DENSE,   // the implicit GEMM, 128 pixels x 128 channels (+ 1: dense rows, + 2: two-term maps)
+    CR_T64, CR_T64_DENSE, CR_T64_PX, CR_T64_PX_DENSE,       // 128 pixels x 64 channels, 48 KiB LDS: three workgroups per CU
+    CR_T256X64,                    // 256 pixels x 64 channels, 80 KiB LDS (fvit_tune "conv64_variant" = 1)
+    CR_COUNT
+};
+// route names = the kernel names of the per-launch profile records (prof_note); bm x bn: the implicit-GEMM tile (pixels x channels)
+struct ConvRouteInfo { const char* name; int bm, bn; };
+constexpr ConvRouteInfo kConvRoutes[CR_COUNT] = {
+    {"conv3x3_c64_halo_kernel", 0, 0},         {"conv3x3_c64_halo_kernel<ln>", 0, 0},
+    {"conv3x3_c128_band_kernel", 0, 0},        {"conv3x3_c128_band_kernel<ln>", 0, 0},
+    {"conv3x3_kernel<2,2,4,patch>", 128, 128}, {"conv3x3_kernel<2,2,4,px,patch>", 128, 128},
+    {"conv3x3_kernel<2,2,4>", 128, 128},       {"conv3x3_kernel<2,2,4,dense>", 128, 128},
+    {"conv3x3_kernel<2,2,4,px>", 128, 128},    {"conv3x3_kernel<2,2,4,px,dense>", 128, 128},
+    {"conv3x3_kernel<2,2,2>", 128, 64},        {"conv3x3_kernel<2,2,2,dense>", 128, 64},
+    {"conv3x3_kernel<2,2,2,px>", 128, 64},     {"conv3x3_kernel<2,2,2,px,dense>", 128, 64},
+    {"conv3x3_kernel<4,1,4>", 256, 64},
+};
+inline bool route_is_ln(int r) { return r == CR_HALO64_LN || r == CR_BAND128_LN; }
+
+// The knobs that select a route, read once per call: fvit_tune takes effect from the next call on, nothing is cached
+struct ConvKnobs {
+    int halo = tune_get("conv_halo", 1), band = tune_get("conv_band", 1);
+    int patch = tune_get("conv_patch", 1), patch_max_waste_pct = tune_get("conv_patch_max_waste_pct", 10);
+    int n128_ragged = tune_get("conv_n128_ragged", 1), narrow = tune_get("conv128_narrow", 0), variant64 = tune_get("conv64_variant", 0);
+};
+
+inline int out_size(int n, int stride) { return (n + 2 - 3) / stride + 1; }
+// the two-term-map kernels (conv3x3_kernel<.., PX>): asked for by name or by any of their planes
+inline bool call_is_px(const FvitConvCall& c) { return c.px || c.in_lo || c.residual_lo || c.out_lo || c.out_f32; }
+
+// Argument validation of every conv entry point (`who` names it in the messages); data pointers are tested, never dereferenced.
+int validate_conv(const char* who, int32_t dtype, const FvitConvWeights* w, const FvitConvCall* c) {
+    if (!w || !c) { set_error("%s: null weights or call", who); return FVIT_EINVAL; }
+    const bool px = call_is_px(*c);
+    if (!c->in || !(w->classic || w->dense || w->band_frag) || (!c->out && !c->out_f32) || !c->zeros || c->B <= 0 || c->Hi <= 0 || c->Wi <= 0 ||
+        c->Cin <= 0 || c->Cout <= 0 || (c->Cin % 64) || (c->Cout % 64) || (c->stride != 1 && c->stride != 2) || c->act < 0 || c->act > 2 ||
+        (w->terms != 1 && w->terms != 2) || (c->in_lo && w->terms != 2) || (c->residual_lo && !c->residual) || (c->out_f32 && c->out_lo) ||
+        (c->out_lo && !c->out)) {
+        set_error("%s: unsupported arguments Cin=%d Cout=%d stride=%d act=%d weight_terms=%d (need Cin %% 64 == 0, Cout %% 64 == 0, stride 1|2, "
+                  "weight_terms 2 with a two-term input, out or out_f32)", who, c->Cin, c->Cout, c->stride, c->act, w->terms);
+        return FVIT_EINVAL;
+    }
+    if (w->cin_valid != c->Cin && (w->cin_valid <= 0 || w->cin_valid > c->Cin || (w->cin_valid % 8))) {
+        set_error("%s: cin_valid=%d must be a multiple of 8 in (0, Cin=%d]", who, w->cin_valid, c->Cin);
+        return FVIT_EINVAL;
+    }
+    const int64_t M = (int64_t)c->B * out_size(c->Hi, c->stride) * out_size(c->Wi, c->stride);
+    if (M > 0x7fffffff) {
+        set_error("%s: %lld output pixels exceed the 32-bit row index", who, (long long)M);
+        return FVIT_EINVAL;
+    }
+    if (c->ln_w && (!c->ln_b || !c->residual || c->stride != 1 || c->act != 0 || px)) {
+        set_error("%s: the LayerNorm2d epilogue needs ln_w and ln_b, a residual, stride 1, no activation and 16-bit maps", who);
+        return FVIT_EINVAL;
+    }
+    if (dtype != FVIT_F16 && dtype != FVIT_BF16) {
+        set_error("%s: dtype %d not supported (16-bit %s only)", who, dtype, px ? "planes" : "maps");
+        return FVIT_EINVAL;
+    }
+    return FVIT_OK;
 }
 
-template <typename T>
-int launch_t(ConvParams& p, hipStream_t stream) {
-    if (p.Cin == 64 && p.Cout == 64 && p.stride == 1 && p.wterms == 1 && !p.px && !p.cv && tune_get("conv_halo", 1)) {
-        if (ablate_skip(64)) return FVIT_OK;
-        return launch_halo_t<T>(p, stream);
-    }
-    if (ablate_skip(32)) return FVIT_OK;
-    const double flops = 2.0 * p.M * (double)p.Cout * 9.0 * (p.cv ? p.cv : p.Cin);
-    const double bytes = 2.0 * ((double)p.B * p.Hi * p.Wi * p.Cin * (p.in_lo ? 2.0 : 1.0) + (double)p.M * p.Cout * ((p.res ? (p.res_lo ? 2.0 : 1.0) : 0.0) + ((p.out_lo || p.out_f32) ? 2.0 : 1.0)) +
-                               9.0 * p.wterms * p.Cin * p.Cout);
-    ProfScope prof(FVIT_K_CONV, flops, bytes, stream);   // (the second weight term is a precision cost, not algorithmic FLOPs)
-    const int variant = tune_get("conv64_variant", 0);
+// The route of a validated call, or CR_NONE with the error message set.  Pure host code.  A route is eligible only if the image it reads is in `w`;
+// with the LayerNorm2d parameters set the answer is an <ln> route where a kernel has that epilogue for the shape and the plain route otherwise.
+ConvRoute choose_conv_route(const FvitConvCall& c, const FvitConvWeights& w, const ConvKnobs& k) {
+    const int Ho = out_size(c.Hi, c.stride), Wo = out_size(c.Wi, c.stride);
+    const int64_t M = (int64_t)c.B * Ho * Wo;
+    const bool px = call_is_px(c), ln = c.ln_w != nullptr;
+    const bool padded = w.cin_valid != c.Cin;   // the map carries pad channels, which only the dense rows leave out of the contraction
+    const bool plain16 = c.stride == 1 && w.terms == 1 && !px && !padded;   // what the two single-purpose kernels take
+    if (c.Cin == 64 && c.Cout == 64 && plain16 && w.classic && k.halo)
+        return ln && M * 64 <= 0x7fffffff ? CR_HALO64_LN : CR_HALO64;
+    // level 1 of FasterViT-0: one row band of an image per workgroup, weights streamed in fragment order
+    if (c.Cin == 128 && c.Cout == 128 && plain16 && w.band_frag && k.band && band_supported(c.Hi, c.Wi) && M * 128 <= 0x7fffffff)
+        return ln ? CR_BAND128_LN : CR_BAND128;
+    // 128-column tiles.  r05 (fvit_tune "conv_n128_ragged", default 1): Cout % 128 == 64 (FasterViT-4: 448 / 832 / 1600 padded channels) also takes them, with
+    // a RAGGED last N tile (weight rows clamped, the missing 64 channels never stored: 1 / (2 n) of the MFMAs wasted) instead of 128 x 64 tiles: half the
+    // workgroups, each weight byte staged for 128 pixels feeds twice the MFMAs, and the weight matrix -- 7.2 MB with two terms at 448 channels, more than an
+    // XCD's 4 MB L2 -- is re-streamed from the Infinity Cache per ROUND of resident workgroups: 3 rounds instead of 11 (PMC: 580 MB read per launch)
+    const bool n128 = c.Cout % 128 == 0 || (c.Cout > 128 && k.n128_ragged);
     // 128x128 tiles run two workgroups per CU (64 KiB LDS): 512 slots.  A grid just above a multiple of 512 pays a whole extra
     // round for a handful of tiles (527 tiles at 86 images of 28x28: 2 rounds, 42 us, of which one full round for 15 tiles).
     // 128x64 tiles (48 KiB, three per CU: 768 slots) do half the MFMA work per workgroup and soften that cliff in isolation
     // (40.6 vs 44 us at 85-86 images, but 41 vs 30 us at 83), yet end to end they lose (68.1k vs 70.0k images/s: the other stream
-    // shards' kernels fill the idle slots of a partial round anyway) => opt-in knob only.
-    const int narrow = tune_get("conv128_narrow", 0);
-    // r06: 8 x 16 output patches with the 10 x 18 halo of a 64-channel chunk in LDS (conv3x3_kernel<.., HALO>): stride 1, classic weight layout, 128-column
-    // tiles; only where the patch grid wastes little (fvit_tune "conv_patch_max_waste_pct", default 10): call 31, two interleaved rounds -- any-res 576 x 960 (144 x 240 and 72 x 120 maps: 0 / 6.7 % waste)
-    // +1.9 % (16-bit plan) / +2.4 % (precise plan); FasterViT-4 224 (56 x 56: 14 % waste, and the classic 36 K steps where the dense-K form walks 29) equal / -0.6 %: stays on the dense-K form
-    const bool patch = patch_form_ok(p) && (p.Cout % 128 == 0 || (p.Cout > 128 && tune_get("conv_n128_ragged", 1))) && !narrow;
-    if (patch) {
-        p.tiles_m = p.B * ((p.Ho + PATCH_H - 1) / PATCH_H) * ((p.Wo + PATCH_W - 1) / PATCH_W);
-        p.tiles_n = (p.Cout + 127) / 128;
-        const dim3 grid_(p.tiles_m * p.tiles_n);
-        prof_note(p.px ? "conv3x3_kernel<2,2,4,px,patch>" : "conv3x3_kernel<2,2,4,patch>", p.tiles_m * p.tiles_n);
-        if (p.px) hipLaunchKernelGGL((conv3x3_kernel<T, 2, 2, 4, true, false, true>), grid_, dim3(256), 0, stream, p);
-        else hipLaunchKernelGGL((conv3x3_kernel<T, 2, 2, 4, false, false, true>), grid_, dim3(256), 0, stream, p);
-        return check_launch("conv3x3_kernel<patch>");
+    // shards' kernels fill the idle slots of a partial round anyway) => "conv128_narrow" is an opt-in knob only.
+    // r06: 8 x 16 output patches with the 10 x 18 halo of a 64-channel chunk in LDS (conv3x3_kernel<.., HALO>): stride 1, classic rows, 128-column tiles, 32-bit
+    // element offsets of the halo rows; only where the patch grid wastes little ("conv_patch_max_waste_pct"): call 31, two interleaved rounds -- any-res
+    // 576 x 960 (144 x 240 and 72 x 120 maps: 0 / 6.7 % waste) +1.9 % (16-bit plan) / +2.4 % (precise plan); FasterViT-4 224 (56 x 56: 14 % waste, and the
+    // classic 36 K steps where the dense-K form walks 29) equal / -0.6 %: stays on the dense-K form
+    if (w.classic && k.patch && c.stride == 1 && c.Cout >= 128 && n128 && !k.narrow && (int64_t)c.B * c.Hi * c.Wi * c.Cin < 0x7fffffffLL) {
+        const int64_t tiles = (int64_t)c.B * ((Ho + PATCH_H - 1) / PATCH_H) * ((Wo + PATCH_W - 1) / PATCH_W);
+        if (tiles * 128 * 100 <= M * (100 + k.patch_max_waste_pct)) return px ? CR_PATCH_PX : CR_PATCH;
     }
-#define FVIT_CONV_LAUNCH(WM_, WN_, NI_, PX_)                                                                                            \
-    do {                                                                                                                                \
-        const dim3 grid_(p.tiles_m * p.tiles_n);                                                                                        \
-        if (p.cv) hipLaunchKernelGGL((conv3x3_kernel<T, WM_, WN_, NI_, PX_, true>), grid_, dim3(256), 0, stream, p);                    \
-        else hipLaunchKernelGGL((conv3x3_kernel<T, WM_, WN_, NI_, PX_, false>), grid_, dim3(256), 0, stream, p);                        \
-    } while (0)
-    if (p.px) {   // two-term maps: the implicit GEMM only (128 x 128 tiles when Cout allows, else 128 x 64)
-        p.tiles_m = (p.M + 127) / 128;
-        if (p.Cout % 128 == 0 || (p.Cout > 128 && tune_get("conv_n128_ragged", 1))) {
-            p.tiles_n = (p.Cout + 127) / 128;
-            prof_note(p.cv ? "conv3x3_kernel<2,2,4,px,dense>" : "conv3x3_kernel<2,2,4,px>", p.tiles_m * p.tiles_n);
-            FVIT_CONV_LAUNCH(2, 2, 4, true);
-        } else {
-            p.tiles_n = p.Cout / 64;
-            prof_note(p.cv ? "conv3x3_kernel<2,2,2,px,dense>" : "conv3x3_kernel<2,2,2,px>", p.tiles_m * p.tiles_n);
-            FVIT_CONV_LAUNCH(2, 2, 2, true);
+    const bool dense = padded && w.dense;
+    if (!dense && !w.classic) {
+        set_error("conv3x3: no kernel for Cin=%d Cout=%d stride=%d on a %d x %d map reads the weight images given (classic%s rows needed)", c.Cin, c.Cout,
+                  c.stride, c.Hi, c.Wi, padded ? " or dense" : "");
+        return CR_NONE;
+    }
+    if (px) return ConvRoute((n128 ? CR_T128_PX : CR_T64_PX) + dense);   // two-term maps: the implicit GEMM only (128 x 128 tiles when Cout allows)
+    if (n128 && !k.narrow) return ConvRoute(CR_T128 + dense);
+    return k.variant64 == 1 && !dense ? CR_T256X64 : ConvRoute(CR_T64 + dense);
+}
+
+using ConvKernel = void (*)(ConvParams);
+template <typename T>
+ConvKernel gemm_kernel(ConvRoute r) {
+    switch (r) {
+    case CR_PATCH: return conv3x3_kernel<T, 2, 2, 4, false, false, true>;
+    case CR_PATCH_PX: return conv3x3_kernel<T, 2, 2, 4, true, false, true>;
+    case CR_T128: return conv3x3_kernel<T, 2, 2, 4, false, false>;
+    case CR_T128_DENSE: return conv3x3_kernel<T, 2, 2, 4, false, true>;
+    case CR_T128_PX: return conv3x3_kernel<T, 2, 2, 4, true, false>;
+    case CR_T128_PX_DENSE: return conv3x3_kernel<T, 2, 2, 4, true, true>;
+    case CR_T64: return conv3x3_kernel<T, 2, 2, 2, false, false>;
+    case CR_T64_DENSE: return conv3x3_kernel<T, 2, 2, 2, false, true>;
+    case CR_T64_PX: return conv3x3_kernel<T, 2, 2, 2, true, false>;
+    case CR_T64_PX_DENSE: return conv3x3_kernel<T, 2, 2, 2, true, true>;
+    default: return conv3x3_kernel<T, 4, 1, 4>;
+    }
+}
+
+// Launches route `r` (from choose_conv_route) of a validated call.  stamps: fvit_debug_conv_band_timeline (CR_BAND128, fp16).
+template <typename T>
+int run_conv(ConvRoute r, const FvitConvCall& c, const FvitConvWeights& w, hipStream_t stream, void* stamps = nullptr) {
+    const char* name = kConvRoutes[r].name;
+    const int Ho = out_size(c.Hi, c.stride), Wo = out_size(c.Wi, c.stride), M = c.B * Ho * Wo;
+    const bool ln = route_is_ln(r);   // the chooser checked: residual epilogue, no activation
+    if (r == CR_HALO64 || r == CR_HALO64_LN) {
+        if (ablate_skip(64)) return FVIT_OK;
+        HaloParams p;
+        p.ln_w = ln ? c.ln_w : nullptr; p.ln_b = c.ln_b; p.ln_eps = c.ln_eps;
+        p.in = c.in; p.w = w.classic; p.bias = c.bias; p.res = c.residual; p.out = c.out; p.zeros = c.zeros;
+        p.B = c.B; p.H = c.Hi; p.W = c.Wi; p.act = c.act;
+        p.tiles_x = (c.Wi + HALO_TW - 1) / HALO_TW; p.tiles_y = (c.Hi + HALO_TH - 1) / HALO_TH;
+        p.tiles = c.B * p.tiles_x * p.tiles_y;   // <= M, which fits int32
+        p.ablate = diag_knob("conv_halo_ablate");
+        int maxgrid = tune_get("conv_halo_grid", 512);   // 2 workgroups per CU (230 VGPRs, 46 KiB LDS each)
+        if (maxgrid < 8) maxgrid = 8;                    // every XCD's tile range needs at least one workgroup
+        const int grid = p.tiles < maxgrid ? p.tiles : maxgrid;
+        ProfScope prof(FVIT_K_CONV, 2.0 * M * 64.0 * 576.0, 2.0 * ((double)M * 64 * (c.residual ? 3.0 : 2.0) + 576.0 * 64), stream);
+        prof_note(name, grid);
+        p.buf_bytes = c.residual ? HALO_BUF : HALO_BYTES;
+        // > 64 KiB of dynamic LDS needs the opt-in attribute (once per device and kernel instance)
+        const void* kern = ln ? (const void*)conv3x3_c64_halo_kernel<T, true> : (const void*)conv3x3_c64_halo_kernel<T>;
+        const size_t lds = ln ? HALO_LN_LDS : 1024 + 2 * (size_t)p.buf_bytes;
+        static DeviceOnce once[2];
+        if (once[ln].first_on_current_device()) hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, ln ? HALO_LN_LDS : 1024 + 2 * HALO_BUF);
+        if (tune_get("conv_halo_debug", 0)) {
+            int nb = -1;
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 256, lds);
+            fprintf(stderr, "[fvit] %s: grid %d, tiles %d, dynamic LDS %zu B, resident workgroups/CU %d\n", name, grid, p.tiles, lds, nb);
         }
-        return check_launch("conv3x3_kernel<px>");
+        if (ln) hipLaunchKernelGGL((conv3x3_c64_halo_kernel<T, true>), dim3(grid), dim3(256), lds, stream, p);
+        else hipLaunchKernelGGL((conv3x3_c64_halo_kernel<T>), dim3(grid), dim3(256), lds, stream, p);
+        return check_launch(name);
     }
-    // r05 (fvit_tune "conv_n128_ragged", default 1): Cout % 128 == 64 (FasterViT-4: 448 / 832 / 1600 padded channels) also takes the 128 x 128 tile with a
-    // RAGGED last N tile (weight rows clamped, the missing 64 channels never stored: 1 / (2 n) of the MFMAs wasted) instead of 128 x 64 tiles: half the
-    // workgroups, each weight byte staged for 128 pixels feeds twice the MFMAs, and the weight matrix -- 7.2 MB with two terms at 448 channels, more than an
-    // XCD's 4 MB L2 -- is re-streamed from the Infinity Cache per ROUND of resident workgroups: 3 rounds instead of 11 (PMC: 580 MB read per launch)
-    if ((p.Cout % 128 == 0 || (p.Cout > 128 && tune_get("conv_n128_ragged", 1))) && !narrow) {
-        p.tiles_m = (p.M + 127) / 128;
-        p.tiles_n = (p.Cout + 127) / 128;
-        prof_note(p.cv ? "conv3x3_kernel<2,2,4,dense>" : "conv3x3_kernel<2,2,4>", p.tiles_m * p.tiles_n);
-        FVIT_CONV_LAUNCH(2, 2, 4, false);
-    } else if (variant == 1 && !p.cv) {  // 256 pixels x 64 channels, 80 KiB LDS
-        p.tiles_m = (p.M + 255) / 256;
-        p.tiles_n = p.Cout / 64;
-        prof_note("conv3x3_kernel<4,1,4>", p.tiles_m * p.tiles_n);
-        hipLaunchKernelGGL((conv3x3_kernel<T, 4, 1, 4>), dim3(p.tiles_m * p.tiles_n), dim3(256), 0, stream, p);
-    } else {  // 128 pixels x 64 channels, 48 KiB LDS: three workgroups per CU
-        p.tiles_m = (p.M + 127) / 128;
-        p.tiles_n = p.Cout / 64;
-        prof_note(p.cv ? "conv3x3_kernel<2,2,2,dense>" : "conv3x3_kernel<2,2,2>", p.tiles_m * p.tiles_n);
-        FVIT_CONV_LAUNCH(2, 2, 2, false);
+    if (ablate_skip(32)) return FVIT_OK;
+    if (r == CR_BAND128 || r == CR_BAND128_LN) {
+        BandParams p;
+        p.in = c.in; p.wf = w.band_frag; p.bias = c.bias; p.res = c.residual; p.out = c.out; p.zeros = c.zeros;
+        p.B = c.B; p.H = c.Hi; p.W = c.Wi; p.act = c.act;
+        p.ln_w = ln ? c.ln_w : nullptr; p.ln_b = c.ln_b; p.ln_eps = c.ln_eps;
+        p.PW = c.Wi + 2;
+        p.R = (BD_NG * 16) / p.PW;
+        if (p.R > c.Hi) p.R = c.Hi;
+        p.bands = (c.Hi + p.R - 1) / p.R;
+        p.npieces = ((p.R + 2) * p.PW + 3) / 4;
+        p.magic = (65536 + p.PW - 1) / p.PW;
+        p.ts = (unsigned long long*)stamps;
+        const dim3 grid(c.B * p.bands);
+        ProfScope prof(FVIT_K_CONV, 2.0 * M * 128.0 * 1152.0, 2.0 * ((double)M * 128 * (c.residual ? 3.0 : 2.0) + 1152.0 * 128), stream);
+        prof_note(name, c.B * p.bands);
+        if (ln) hipLaunchKernelGGL((conv3x3_c128_band_kernel<T, false, true>), grid, dim3(256), 0, stream, p);
+        else if (std::is_same<T, _Float16>::value && stamps) hipLaunchKernelGGL((conv3x3_c128_band_kernel<_Float16, true>), grid, dim3(256), 0, stream, p);
+        else hipLaunchKernelGGL((conv3x3_c128_band_kernel<T>), grid, dim3(256), 0, stream, p);
+        return check_launch(name);
     }
-    return check_launch("conv3x3_kernel");
-#undef FVIT_CONV_LAUNCH
+    // the implicit GEMM: dense rows contract over cv real channels per tap, kd K steps; classic rows (cv = 0) over all Cin
+    const bool px = call_is_px(c), dense = r >= CR_T128 && ((r - CR_T128) & 1), patch = r == CR_PATCH || r == CR_PATCH_PX;
+    ConvParams p;
+    p.in = c.in; p.w = dense ? w.dense : w.classic; p.bias = c.bias; p.res = c.residual; p.out = c.out; p.zeros = c.zeros;
+    p.B = c.B; p.Hi = c.Hi; p.Wi = c.Wi; p.Cin = c.Cin; p.Cout = c.Cout; p.Ho = Ho; p.Wo = Wo; p.stride = c.stride; p.act = c.act; p.M = M;
+    p.ablate = px ? 0 : diag_knob("conv_ablate"); p.wterms = w.terms;
+    p.in_lo = c.in_lo; p.res_lo = c.residual_lo; p.out_lo = c.out_lo; p.out_f32 = c.out_f32; p.px = px;
+    p.cv = dense ? w.cin_valid : 0; p.kd = dense ? (9 * p.cv + BK - 1) / BK : 0; p.inv_cv = dense ? 1.0f / (float)p.cv : 0.f;
+    p.tiles_m = patch ? c.B * ((Ho + PATCH_H - 1) / PATCH_H) * ((Wo + PATCH_W - 1) / PATCH_W) : (M + kConvRoutes[r].bm - 1) / kConvRoutes[r].bm;
+    p.tiles_n = (c.Cout + kConvRoutes[r].bn - 1) / kConvRoutes[r].bn;   // 128-column tiles: the last one may be ragged
+    const double flops = 2.0 * M * (double)c.Cout * 9.0 * (dense ? p.cv : c.Cin);
+    const double bytes = 2.0 * ((double)c.B * c.Hi * c.Wi * c.Cin * (c.in_lo ? 2.0 : 1.0) +
+                                (double)M * c.Cout * ((c.residual ? (c.residual_lo ? 2.0 : 1.0) : 0.0) + ((c.out_lo || c.out_f32) ? 2.0 : 1.0)) + 9.0 * w.terms * c.Cin * c.Cout);
+    ProfScope prof(FVIT_K_CONV, flops, bytes, stream);   // (the second weight term is a precision cost, not algorithmic FLOPs)
+    prof_note(name, p.tiles_m * p.tiles_n);
+    hipLaunchKernelGGL(gemm_kernel<T>(r), dim3(p.tiles_m * p.tiles_n), dim3(256), 0, stream, p);
+    return check_launch(name);
+}
+
+int launch_route(int32_t dtype, ConvRoute r, const FvitConvCall& c, const FvitConvWeights& w, fvit_stream_t stream, void* stamps = nullptr) {
+    return dtype == FVIT_F16 ? run_conv<_Float16>(r, c, w, (hipStream_t)stream, stamps) : run_conv<__bf16>(r, c, w, (hipStream_t)stream, stamps);
+}
+
+// validate and choose, then launch (`run`: FVIT_OK or a negative error) or answer the route (>= 0, or a negative error)
+int conv_entry(int32_t dtype, const FvitConvWeights* w, const FvitConvCall* c, bool run, fvit_stream_t stream) {
+    const char* who = c && call_is_px(*c) ? "conv3x3_px" : "conv3x3";
+    if (const int rc = validate_conv(who, dtype, w, c)) return rc;
+    const ConvRoute r = choose_conv_route(*c, *w, ConvKnobs{});
+    if (r == CR_NONE) return FVIT_EINVAL;
+    if (!run) return r;
+    if (c->ln_w && !route_is_ln(r)) {
+        set_error("%s: %s has no LayerNorm2d epilogue (ask fvit_conv3x3_route first and run the LayerNorm2d pass apart)", who, kConvRoutes[r].name);
+        return FVIT_EINVAL;
+    }
+    return launch_route(dtype, r, *c, *w, stream);
+}
+
+// the structs of an entry point that is given ONE weight image
+FvitConvCall one_call(const void* in, const float* bias, const void* residual, void* out, const void* zeros, int B, int Hi, int Wi, int Cin, int Cout,
+                      int stride, int act) {
+    FvitConvCall c{};
+    c.in = in; c.bias = bias; c.residual = residual; c.out = out; c.zeros = zeros;
+    c.B = B; c.Hi = Hi; c.Wi = Wi; c.Cin = Cin; c.Cout = Cout; c.stride = stride; c.act = act;
+    return c;
+}
+int one_image_conv(int32_t dtype, FvitConvCall c, const void* weight, int cin_valid, int terms, fvit_stream_t stream) {
+    FvitConvWeights w{};
+    (cin_valid == c.Cin ? w.classic : w.dense) = weight;
+    w.terms = terms; w.cin_valid = cin_valid;
+    return conv_entry(dtype, &w, &c, true, stream);
+}
+// the row-band / LayerNorm2d entry points name their kernel (`want`): its knob does not switch them off, any other route is their FVIT_EINVAL
+static_assert(BD_MAXPW == 32, "the W <= 30 in the messages of the row-band entry points");
+int named_conv(const char* who, const char* need, int32_t dtype, FvitConvCall c, const void* classic, const void* band_frag, ConvRoute want, const float* ln_w,
+               const float* ln_b, float eps, fvit_stream_t stream, void* stamps = nullptr) {
+    const FvitConvWeights w{classic, nullptr, band_frag, 1, c.Cin};
+    c.ln_w = ln_w; c.ln_b = ln_b; c.ln_eps = eps;
+    ConvKnobs k;
+    k.halo = k.band = 1;
+    if (validate_conv(who, dtype, &w, &c) == FVIT_OK && choose_conv_route(c, w, k) == want) return launch_route(dtype, want, c, w, stream, stamps);
+    if (dtype == FVIT_F16 || dtype == FVIT_BF16) set_error("%s: unsupported arguments B=%d H=%d W=%d act=%d (need %s)", who, c.B, c.Hi, c.Wi, c.act, need);
+    return FVIT_EINVAL;
 }
 
 }  // namespace
@@ -1659,85 +1755,40 @@ int launch_t(ConvParams& p, hipStream_t stream) {
 
 using namespace fvit;
 
-extern "C" int fvit_conv3x3_nhwc_terms(int32_t dtype, const void* in, const void* weight, const float* bias, const void* residual, void* out,
-                                       int32_t B, int32_t Hi, int32_t Wi, int32_t Cin, int32_t Cout, int32_t stride, int32_t act,
-                                       int32_t weight_terms, const void* zeros, fvit_stream_t stream);
-extern "C" int fvit_conv3x3_nhwc_dense(int32_t dtype, const void* in, const void* weight, const float* bias, const void* residual, void* out,
-                                       int32_t B, int32_t Hi, int32_t Wi, int32_t Cin, int32_t cin_valid, int32_t Cout, int32_t stride, int32_t act,
-                                       int32_t weight_terms, const void* zeros, fvit_stream_t stream);
+extern "C" int fvit_conv3x3(int32_t dtype, const FvitConvWeights* weights, const FvitConvCall* call, fvit_stream_t stream) { return conv_entry(dtype, weights, call, true, stream); }
+
+extern "C" int fvit_conv3x3_route(int32_t dtype, const FvitConvWeights* weights, const FvitConvCall* call) { return conv_entry(dtype, weights, call, false, nullptr); }
+
+extern "C" const char* fvit_conv3x3_route_name(int route) { return route >= 0 && route < CR_COUNT ? kConvRoutes[route].name : "?"; }
+
+extern "C" int fvit_conv3x3_dense_k(int32_t cin_valid) { return cin_valid > 0 && cin_valid % 8 == 0 ? (9 * cin_valid + BK - 1) / BK * BK : -1; }
 
 extern "C" int fvit_conv3x3_nhwc(int32_t dtype, const void* in, const void* weight, const float* bias, const void* residual, void* out,
                                  int32_t B, int32_t Hi, int32_t Wi, int32_t Cin, int32_t Cout, int32_t stride, int32_t act,
                                  const void* zeros, fvit_stream_t stream) {
-    return fvit_conv3x3_nhwc_terms(dtype, in, weight, bias, residual, out, B, Hi, Wi, Cin, Cout, stride, act, 1, zeros, stream);
+    return one_image_conv(dtype, one_call(in, bias, residual, out, zeros, B, Hi, Wi, Cin, Cout, stride, act), weight, Cin, 1, stream);
 }
-
-// dense-K parameters of a launch: cin_valid == Cin -> the classic [Cout][terms][3][3][Cin] weight matrix; cin_valid < Cin -> the dense matrix
-// [Cout][terms][kd * 64] (fvit_hip.h, fvit_conv3x3_dense_k)
-static bool set_dense(ConvParams& p, int cin_valid) {
-    p.cv = 0; p.kd = 0; p.inv_cv = 0.f;
-    if (cin_valid == p.Cin) return true;
-    if (cin_valid <= 0 || cin_valid > p.Cin || (cin_valid % 8)) return false;
-    p.cv = cin_valid;
-    p.kd = (9 * cin_valid + BK - 1) / BK;
-    p.inv_cv = 1.0f / (float)cin_valid;
-    return true;
-}
-
-extern "C" int fvit_conv3x3_patch_form(int32_t B, int32_t Hi, int32_t Wi, int32_t Cin, int32_t Cout, int32_t stride) {
-    if (B <= 0 || Hi <= 0 || Wi <= 0 || Cin <= 0 || Cout <= 0) return 0;
-    ConvParams p;
-    p.B = B; p.Hi = Hi; p.Wi = Wi; p.Cin = Cin; p.Cout = Cout; p.stride = stride; p.cv = 0;
-    p.Ho = (Hi + 2 - 3) / stride + 1; p.Wo = (Wi + 2 - 3) / stride + 1;
-    p.M = B * p.Ho * p.Wo;
-    return patch_form_ok(p) && (Cout % 128 == 0 || (Cout > 128 && tune_get("conv_n128_ragged", 1))) && !tune_get("conv128_narrow", 0) ? 1 : 0;
-}
-
-extern "C" int fvit_conv3x3_dense_k(int32_t cin_valid) { return cin_valid > 0 && cin_valid % 8 == 0 ? (9 * cin_valid + BK - 1) / BK * BK : -1; }
 
 extern "C" int fvit_conv3x3_nhwc_terms(int32_t dtype, const void* in, const void* weight, const float* bias, const void* residual, void* out,
                                        int32_t B, int32_t Hi, int32_t Wi, int32_t Cin, int32_t Cout, int32_t stride, int32_t act,
                                        int32_t weight_terms, const void* zeros, fvit_stream_t stream) {
-    return fvit_conv3x3_nhwc_dense(dtype, in, weight, bias, residual, out, B, Hi, Wi, Cin, Cin, Cout, stride, act, weight_terms, zeros, stream);
+    return one_image_conv(dtype, one_call(in, bias, residual, out, zeros, B, Hi, Wi, Cin, Cout, stride, act), weight, Cin, weight_terms, stream);
 }
 
 extern "C" int fvit_conv3x3_nhwc_dense(int32_t dtype, const void* in, const void* weight, const float* bias, const void* residual, void* out,
                                        int32_t B, int32_t Hi, int32_t Wi, int32_t Cin, int32_t cin_valid, int32_t Cout, int32_t stride, int32_t act,
                                        int32_t weight_terms, const void* zeros, fvit_stream_t stream) {
-    if (!in || !weight || !out || !zeros || B <= 0 || Hi <= 0 || Wi <= 0 || Cin <= 0 || Cout <= 0 || (Cin % 64) || (Cout % 64) ||
-        (stride != 1 && stride != 2) || act < 0 || act > 2 || (weight_terms != 1 && weight_terms != 2)) {
-        set_error("conv3x3: unsupported arguments Cin=%d Cout=%d stride=%d act=%d (need Cin %% 64 == 0, Cout %% 64 == 0, stride 1|2)",
-                  Cin, Cout, stride, act);
-        return FVIT_EINVAL;
-    }
-    ConvParams p;
-    p.in = in; p.w = weight; p.bias = bias; p.res = residual; p.out = out; p.zeros = zeros;
-    p.B = B; p.Hi = Hi; p.Wi = Wi; p.Cin = Cin; p.Cout = Cout; p.stride = stride; p.act = act;
-    p.ablate = diag_knob("conv_ablate");
-    p.wterms = weight_terms;
-    p.in_lo = p.res_lo = nullptr; p.out_lo = nullptr; p.out_f32 = nullptr; p.px = 0;
-    if (!set_dense(p, cin_valid)) {
-        set_error("conv3x3: cin_valid=%d must be a multiple of 8 in (0, Cin=%d]", cin_valid, Cin);
-        return FVIT_EINVAL;
-    }
-    p.Ho = (Hi + 2 - 3) / stride + 1;
-    p.Wo = (Wi + 2 - 3) / stride + 1;
-    const int64_t M = (int64_t)B * p.Ho * p.Wo;
-    if (M > 0x7fffffff) {
-        set_error("conv3x3: %lld output pixels exceed the 32-bit row index", (long long)M);
-        return FVIT_EINVAL;
-    }
-    p.M = (int)M;
-    if (dtype == FVIT_F16) return launch_t<_Float16>(p, (hipStream_t)stream);
-    if (dtype == FVIT_BF16) return launch_t<__bf16>(p, (hipStream_t)stream);
-    set_error("conv3x3: dtype %d not supported (16-bit maps only)", dtype);
-    return FVIT_EINVAL;
+    return one_image_conv(dtype, one_call(in, bias, residual, out, zeros, B, Hi, Wi, Cin, Cout, stride, act), weight, cin_valid, weight_terms, stream);
 }
 
 extern "C" int fvit_conv3x3_nhwc_px_dense(int32_t dtype, const void* in, const void* in_lo, const void* weight, const float* bias, const void* residual,
                                           const void* residual_lo, void* out, void* out_lo, float* out_f32, int32_t B, int32_t Hi, int32_t Wi, int32_t Cin,
                                           int32_t cin_valid, int32_t Cout, int32_t stride, int32_t act, int32_t weight_terms, const void* zeros,
-                                          fvit_stream_t stream);
+                                          fvit_stream_t stream) {
+    FvitConvCall c = one_call(in, bias, residual, out, zeros, B, Hi, Wi, Cin, Cout, stride, act);
+    c.in_lo = in_lo; c.residual_lo = residual_lo; c.out_lo = out_lo; c.out_f32 = out_f32; c.px = 1;
+    return one_image_conv(dtype, c, weight, cin_valid, weight_terms, stream);
+}
 
 extern "C" int fvit_conv3x3_nhwc_px(int32_t dtype, const void* in, const void* in_lo, const void* weight, const float* bias, const void* residual,
                                     const void* residual_lo, void* out, void* out_lo, float* out_f32, int32_t B, int32_t Hi, int32_t Wi, int32_t Cin,
@@ -1746,40 +1797,48 @@ extern "C" int fvit_conv3x3_nhwc_px(int32_t dtype, const void* in, const void* i
                                       weight_terms, zeros, stream);
 }
 
-extern "C" int fvit_conv3x3_nhwc_px_dense(int32_t dtype, const void* in, const void* in_lo, const void* weight, const float* bias, const void* residual,
-                                          const void* residual_lo, void* out, void* out_lo, float* out_f32, int32_t B, int32_t Hi, int32_t Wi, int32_t Cin,
-                                          int32_t cin_valid, int32_t Cout, int32_t stride, int32_t act, int32_t weight_terms, const void* zeros,
-                                          fvit_stream_t stream) {
-    if (!in || !weight || (!out && !out_f32) || !zeros || B <= 0 || Hi <= 0 || Wi <= 0 || Cin <= 0 || Cout <= 0 || (Cin % 64) || (Cout % 64) ||
-        (stride != 1 && stride != 2) || act < 0 || act > 2 || (weight_terms != 1 && weight_terms != 2) || (in_lo && weight_terms != 2) ||
-        (residual_lo && !residual) || (out_f32 && out_lo) || (out_lo && !out)) {
-        set_error("conv3x3_px: unsupported arguments Cin=%d Cout=%d stride=%d act=%d weight_terms=%d (need Cin %% 64 == 0, Cout %% 64 == 0, stride 1|2, "
-                  "weight_terms 2 with a two-term input, out or out_f32)", Cin, Cout, stride, act, weight_terms);
-        return FVIT_EINVAL;
-    }
-    ConvParams p;
-    p.in = in; p.w = weight; p.bias = bias; p.res = residual; p.out = out; p.zeros = zeros;
-    p.B = B; p.Hi = Hi; p.Wi = Wi; p.Cin = Cin; p.Cout = Cout; p.stride = stride; p.act = act;
-    p.ablate = 0;
-    p.wterms = weight_terms;
-    p.in_lo = in_lo; p.res_lo = residual_lo; p.out_lo = out_lo; p.out_f32 = out_f32; p.px = 1;
-    if (!set_dense(p, cin_valid)) {
-        set_error("conv3x3_px: cin_valid=%d must be a multiple of 8 in (0, Cin=%d]", cin_valid, Cin);
-        return FVIT_EINVAL;
-    }
-    p.Ho = (Hi + 2 - 3) / stride + 1;
-    p.Wo = (Wi + 2 - 3) / stride + 1;
-    const int64_t M = (int64_t)B * p.Ho * p.Wo;
-    if (M > 0x7fffffff) {
-        set_error("conv3x3_px: %lld output pixels exceed the 32-bit row index", (long long)M);
-        return FVIT_EINVAL;
-    }
-    p.M = (int)M;
-    if (dtype == FVIT_F16) return launch_t<_Float16>(p, (hipStream_t)stream);
-    if (dtype == FVIT_BF16) return launch_t<__bf16>(p, (hipStream_t)stream);
-    set_error("conv3x3_px: dtype %d not supported (16-bit planes only)", dtype);
-    return FVIT_EINVAL;
+// given classic rows, does the driver take the patch form for this shape?  (Any non-null address stands for the image.)
+extern "C" int fvit_conv3x3_patch_form(int32_t B, int32_t Hi, int32_t Wi, int32_t Cin, int32_t Cout, int32_t stride) {
+    const FvitConvWeights w{&w, nullptr, nullptr, 2, Cin};
+    const FvitConvCall c = one_call(&w, nullptr, nullptr, (void*)&w, &w, B, Hi, Wi, Cin, Cout, stride, 0);
+    return conv_entry(FVIT_F16, &w, &c, false, nullptr) == CR_PATCH ? 1 : 0;
 }
+
+extern "C" int fvit_conv3x3_c128_band_supported(int32_t H, int32_t W) {
+    const FvitConvWeights w{nullptr, nullptr, &w, 1, 128};
+    const FvitConvCall c = one_call(&w, nullptr, nullptr, (void*)&w, &w, 1, H, W, 128, 128, 1, 0);
+    return conv_entry(FVIT_F16, &w, &c, false, nullptr) == CR_BAND128 ? 1 : 0;
+}
+
+extern "C" int fvit_conv3x3_c128_band(int32_t dtype, const void* in, const void* w_frag, const float* bias, const void* residual, void* out,
+                                      int32_t B, int32_t H, int32_t W, int32_t act, const void* zeros, fvit_stream_t stream) {
+    return named_conv("conv3x3_c128_band", "W <= 30", dtype, one_call(in, bias, residual, out, zeros, B, H, W, 128, 128, 1, act), nullptr, w_frag, CR_BAND128,
+                      nullptr, nullptr, 0.f, stream);
+}
+
+extern "C" int fvit_conv3x3_c64_ln2d(int32_t dtype, const void* in, const void* weight, const float* bias, const void* residual, void* out,
+                                     const float* ln_w, const float* ln_b, float eps, int32_t B, int32_t H, int32_t W, const void* zeros,
+                                     fvit_stream_t stream) {
+    return named_conv("conv3x3_c64_ln2d", "a residual and LayerNorm2d parameters", dtype, one_call(in, bias, residual, out, zeros, B, H, W, 64, 64, 1, 0), weight,
+                      nullptr, CR_HALO64_LN, ln_w, ln_b, eps, stream);
+}
+
+extern "C" int fvit_conv3x3_c128_band_ln2d(int32_t dtype, const void* in, const void* w_frag, const float* bias, const void* residual, void* out,
+                                           const float* ln_w, const float* ln_b, float eps, int32_t B, int32_t H, int32_t W, const void* zeros,
+                                           fvit_stream_t stream) {
+    return named_conv("conv3x3_c128_band_ln2d", "a residual, LayerNorm2d parameters and W <= 30", dtype,
+                      one_call(in, bias, residual, out, zeros, B, H, W, 128, 128, 1, 0), nullptr, w_frag, CR_BAND128_LN, ln_w, ln_b, eps, stream);
+}
+
+// diagnosis: the fp16 row-band kernel with s_memtime stamps, u64 [B * bands][4 waves][8] (see BandParams.ts); bands = ceil(H / (224 / (W + 2)))
+#ifdef FVIT_DIAG
+extern "C" int fvit_debug_conv_band_timeline(const void* in, const void* w_frag, const float* bias, const void* residual, void* out, int32_t B,
+                                             int32_t H, int32_t W, int32_t act, const void* zeros, void* stamps, fvit_stream_t stream) {
+    if (!stamps) { set_error("debug_conv_band_timeline: null stamp buffer"); return FVIT_EINVAL; }
+    return named_conv("debug_conv_band_timeline", "W <= 30", FVIT_F16, one_call(in, bias, residual, out, zeros, B, H, W, 128, 128, 1, act), nullptr, w_frag,
+                      CR_BAND128, nullptr, nullptr, 0.f, stream, stamps);
+}
+#endif  // FVIT_DIAG
 
 extern "C" int fvit_stem_conv3x3s2_px(int32_t dtype, const FvitMapView* in, const void* weight, const void* weight_lo, const float* bias, void* out,
                                       int32_t B, int32_t Hi, int32_t Wi, fvit_stream_t stream);
@@ -1908,65 +1967,3 @@ static int stem_fused_impl(int32_t dtype, const FvitMapView* in, const void* w1,
 #undef FVIT_STEM_LAUNCH
     return check_launch("stem_fused_kernel");
 }
-
-extern "C" int fvit_conv3x3_c128_band_supported(int32_t H, int32_t W) { return band_supported(H, W) && tune_get("conv_band", 1) ? 1 : 0; }
-
-extern "C" int fvit_conv3x3_c128_band(int32_t dtype, const void* in, const void* w_frag, const float* bias, const void* residual, void* out,
-                                      int32_t B, int32_t H, int32_t W, int32_t act, const void* zeros, fvit_stream_t stream) {
-    if (!in || !w_frag || !out || !zeros || B <= 0 || !band_supported(H, W) || act < 0 || act > 2 || (int64_t)B * H * W * 128 > 0x7fffffff) {
-        set_error("conv3x3_c128_band: unsupported arguments B=%d H=%d W=%d act=%d (need W <= %d)", B, H, W, act, BD_MAXPW - 2);
-        return FVIT_EINVAL;
-    }
-    if (ablate_skip(32)) return FVIT_OK;
-    if (dtype == FVIT_F16) return launch_band_t<_Float16>(in, w_frag, bias, residual, out, zeros, B, H, W, act, (hipStream_t)stream);
-    if (dtype == FVIT_BF16) return launch_band_t<__bf16>(in, w_frag, bias, residual, out, zeros, B, H, W, act, (hipStream_t)stream);
-    set_error("conv3x3_c128_band: dtype %d not supported (16-bit maps only)", dtype);
-    return FVIT_EINVAL;
-}
-
-// The conv that ends a 64-channel level with the following Downsample's LayerNorm2d in its epilogue (conv3x3_c64_halo_kernel<.., LN>):
-// out = LayerNorm2d(round16(conv3x3(in) + bias + residual)) over the 64 channels of a pixel.  weight: [64][3][3][64]; residual may alias out.
-extern "C" int fvit_conv3x3_c64_ln2d(int32_t dtype, const void* in, const void* weight, const float* bias, const void* residual, void* out,
-                                     const float* ln_w, const float* ln_b, float eps, int32_t B, int32_t H, int32_t W, const void* zeros,
-                                     fvit_stream_t stream) {
-    if (!in || !weight || !residual || !out || !ln_w || !ln_b || !zeros || B <= 0 || H <= 0 || W <= 0 || (int64_t)B * H * W * 64 > 0x7fffffff) {
-        set_error("conv3x3_c64_ln2d: unsupported arguments B=%d H=%d W=%d (need a residual and LayerNorm2d parameters)", B, H, W);
-        return FVIT_EINVAL;
-    }
-    if (ablate_skip(64)) return FVIT_OK;
-    ConvParams p;
-    p.in = in; p.w = weight; p.bias = bias; p.res = residual; p.out = out; p.zeros = zeros;
-    p.B = B; p.Hi = p.Ho = H; p.Wi = p.Wo = W; p.Cin = p.Cout = 64; p.stride = 1; p.act = 0; p.M = B * H * W;
-    if (dtype == FVIT_F16) return launch_halo_t<_Float16>(p, (hipStream_t)stream, ln_w, ln_b, eps);
-    if (dtype == FVIT_BF16) return launch_halo_t<__bf16>(p, (hipStream_t)stream, ln_w, ln_b, eps);
-    set_error("conv3x3_c64_ln2d: dtype %d not supported (16-bit maps only)", dtype);
-    return FVIT_EINVAL;
-}
-
-// The conv that ends a level with the following Downsample's LayerNorm2d in its epilogue: out = LayerNorm2d(round16(conv + bias + residual)) over the 128
-// channels of a pixel (conv3x3_c128_band_kernel<.., LN>).  residual may alias out.
-extern "C" int fvit_conv3x3_c128_band_ln2d(int32_t dtype, const void* in, const void* w_frag, const float* bias, const void* residual, void* out,
-                                           const float* ln_w, const float* ln_b, float eps, int32_t B, int32_t H, int32_t W, const void* zeros,
-                                           fvit_stream_t stream) {
-    if (!in || !w_frag || !residual || !out || !ln_w || !ln_b || !zeros || B <= 0 || !band_supported(H, W) || (int64_t)B * H * W * 128 > 0x7fffffff) {
-        set_error("conv3x3_c128_band_ln2d: unsupported arguments B=%d H=%d W=%d (need a residual, LayerNorm2d parameters and W <= %d)", B, H, W, BD_MAXPW - 2);
-        return FVIT_EINVAL;
-    }
-    if (ablate_skip(32)) return FVIT_OK;
-    if (dtype == FVIT_F16) return launch_band_t<_Float16>(in, w_frag, bias, residual, out, zeros, B, H, W, 0, (hipStream_t)stream, nullptr, ln_w, ln_b, eps);
-    if (dtype == FVIT_BF16) return launch_band_t<__bf16>(in, w_frag, bias, residual, out, zeros, B, H, W, 0, (hipStream_t)stream, nullptr, ln_w, ln_b, eps);
-    set_error("conv3x3_c128_band_ln2d: dtype %d not supported (16-bit maps only)", dtype);
-    return FVIT_EINVAL;
-}
-
-// diagnosis: the fp16 kernel with s_memtime stamps, u64 [B * bands][4 waves][8] (see BandParams.ts); bands = ceil(H / (224 / (W + 2)))
-#ifdef FVIT_DIAG
-extern "C" int fvit_debug_conv_band_timeline(const void* in, const void* w_frag, const float* bias, const void* residual, void* out, int32_t B,
-                                             int32_t H, int32_t W, int32_t act, const void* zeros, void* stamps, fvit_stream_t stream) {
-    if (!in || !w_frag || !out || !zeros || !stamps || B <= 0 || !band_supported(H, W) || act < 0 || act > 2) {
-        set_error("debug_conv_band_timeline: unsupported arguments");
-        return FVIT_EINVAL;
-    }
-    return launch_band_t<_Float16>(in, w_frag, bias, residual, out, zeros, B, H, W, act, (hipStream_t)stream, stamps);
-}
-#endif  // FVIT_DIAG

@@ -480,60 +480,110 @@ int fvit_layernorm2d_crop_cl(int32_t dtype, const void* in, void* out, const flo
  * fp32 sums in a fixed order (bitwise repeatable).  With fvit_head_logits the tail of the deploy plan: no library kernel in the timed graph. */
 int fvit_global_avgpool_cl(int32_t dtype, const void* in, float* out, int32_t B, int32_t HW, int32_t C, fvit_stream_t stream);
 
-/* 3x3 convolution, pad 1, stride 1 or 2, on channels-last 16-bit maps as an implicit GEMM on the MFMA cores with the
- * epilogue fused: out = act(conv(in, weight) + bias) (+ residual).  Replaces (deploy mode, BatchNorm folded into
- * weight/bias) conv + BN + ReLU of PatchEmbed (FV:462-464), conv-BN-GELU / conv-BN-gamma-residual of ConvBlock
- * (FV:502-512) and Downsample.reduction (FV:435).
- *   in [B][Hi][Wi][Cin], weight [Cout][3][3][Cin] (= channels_last storage of the PyTorch weight), bias f32 [Cout] or
- *   NULL, residual [B][Ho][Wo][Cout] or NULL (may alias out), out [B][Ho][Wo][Cout]; act 0 none / 1 ReLU / 2 GELU;
- *   zeros: >= 128 bytes of zeros (padding taps read it).  Needs Cin % 64 == 0 and Cout % 64 == 0. */
+/* ---- 3x3 convolution (pad 1, stride 1 or 2) on channels-last 16-bit maps: the conv driver ------------------------------------------------
+ *     out = act(conv(in, weight) + bias) (+ residual)          act 0 none / 1 ReLU / 2 GELU
+ * on the MFMA cores with the whole epilogue fused.  Replaces (deploy mode, BatchNorm folded into weight / bias) conv + BN + ReLU of PatchEmbed
+ * (FV:462-464), conv-BN-GELU / conv-BN-gamma-residual of ConvBlock (FV:502-512) and Downsample.reduction (FV:435).  Needs Cin % 64 == 0 and
+ * Cout % 64 == 0.  The caller hands over every image of the weights it has packed and one call description; the driver (fvit_conv.hip:
+ * choose_conv_route, run_conv) picks the kernel -- a route is eligible only if the image it reads is there -- and launches it.
+ *
+ * FvitConvWeights -- the packed images of ONE conv (NULL = not packed), each op16:
+ *   classic    [Cout][terms][3][3][Cin] (terms 1: the channels_last storage of the PyTorch weight).  terms = 2: [hi | lo] per output channel,
+ *              hi = round(w), lo = round(w - hi): the lo image's K steps re-read the activation tile, the weights carry ~22 bits while the maps
+ *              stay 16-bit (the Downsample convs' weight rounding is systematic: 2.4e-4 / 1.7e-4 / 2.1e-4 of FasterViT-0's 4.2e-4 conv-side error)
+ *   dense      dense K, for a map whose Cin channels hold only cin_valid real ones (FasterViT-4: 196 of 256, 392 of 448): [Cout][terms][kd],
+ *              kd = fvit_conv3x3_dense_k(cin_valid) = 9 * cin_valid rounded up to 64 (-1: unsupported), column t * cin_valid + c = w[co][tap t][c],
+ *              the tail zero.  Cin stays the channel STRIDE of the map; cin_valid % 8 == 0.  Ignored when cin_valid == Cin
+ *   band_frag  Cin = Cout = 128, terms 1: the MFMA-fragment-order stream of the row-band kernel, [4][36][2][64][8]: element e of lane 16 g + s of
+ *              fragment (wave, step, ni) = classic[32 wave + (s >> 2) * 8 + ni * 4 + (s & 3)][step * 32 + 8 g + e]
+ * FvitConvCall -- one launch:
+ *   in / in_lo, residual / residual_lo, out / out_lo, out_f32
+ *              [B][Hi][Wi][Cin] in, [B][Ho][Wo][Cout] residual (may alias out) and out.  The *_lo planes, out_f32 and px select the TWO-TERM MAP
+ *              kernels (r05, the "precise" deploy plan): a stream is a pair of 16-bit planes (value = hi + lo, lo = round(v - hi), ~22 bits) or, next
+ *              to a transformer level, one fp32 map -- a rounded stored stream costs 3-4e-4 of logits error each on FasterViT-4, a rounded conv
+ *              operand 2-8e-5 (tests/tools/conv_precision_sim.py).  in_lo (needs terms 2): in.w_hi + in.w_lo + in_lo.w_hi; residual planes are
+ *              added in fp32; out_lo = round(y - hi); out_f32 instead of out / out_lo.  px = 1 asks for these kernels without any of the planes
+ *              (their GELU is the 1.5e-7-accurate erf form, the 16-bit kernels use a 5e-5 polynomial)
+ *   ln_w, ln_b, ln_eps
+ *              f32 [Cout] or NULL.  Set: out = LayerNorm2d(round16(conv + bias + residual)) * ln_w + ln_b over the channels of a pixel -- the
+ *              following Downsample's LayerNorm2d of exactly the 16-bit map the plain kernel stores (fp32 statistics, two passes) without that
+ *              map's round trip through HBM.  Needs a residual, stride 1, act 0, and a route whose name ends in "<ln>" (64 -> 64 channels with
+ *              classic single-term rows; 128 -> 128 with band_frag and Wi <= 30): ask fvit_conv3x3_route first, fvit_conv3x3 refuses otherwise
+ *   zeros      >= 256 bytes of zeros (padding taps read it)
+ * fvit_conv3x3        chooses the route and runs it.
+ * fvit_conv3x3_route  host only, the data pointers are tested against NULL and never dereferenced: the route id fvit_conv3x3 would take now
+ *                     (fvit_tune knobs included) or a negative error; fvit_conv3x3_route_name gives its name, which is also the kernel name of
+ *                     the launch's fvit_prof_records entry ("conv3x3_c64_halo_kernel<ln>", "conv3x3_kernel<2,2,4,patch>", ...; "?" for no route).
+ * Routes: the register-stationary 64 -> 64 halo kernel; the 128 -> 128 row-band kernel (one band of full-width rows per workgroup, weights streamed
+ * in fragment order); the PATCH form of the implicit GEMM (r06: 8 x 16 output patches, the 10 x 18 halo of a 64-channel chunk staged once for all
+ * nine taps and both terms: stride 1, Cout >= 128, classic rows, a patch grid that wastes <= fvit_tune("conv_patch_max_waste_pct") = 10 %);
+ * the implicit GEMM in 128 x 128 / 128 x 64 / 256 x 64 tiles over classic or dense rows. */
+typedef struct FvitConvWeights {
+    const void* classic;
+    const void* dense;
+    const void* band_frag;
+    int32_t terms;       /* weight terms of classic / dense: 1 or 2 */
+    int32_t cin_valid;   /* real channels of the input map (== Cin: no pad channels) */
+} FvitConvWeights;
+typedef struct FvitConvCall {
+    const void* in;
+    const void* in_lo;
+    const float* bias;   /* f32 [Cout] or NULL */
+    const void* residual;
+    const void* residual_lo;
+    void* out;
+    void* out_lo;
+    float* out_f32;
+    const float* ln_w;
+    const float* ln_b;
+    const void* zeros;
+    float ln_eps;
+    int32_t B, Hi, Wi, Cin, Cout, stride, act;
+    int32_t px;
+} FvitConvCall;
+int fvit_conv3x3(int32_t dtype, const FvitConvWeights* weights, const FvitConvCall* call, fvit_stream_t stream);
+int fvit_conv3x3_route(int32_t dtype, const FvitConvWeights* weights, const FvitConvCall* call);
+const char* fvit_conv3x3_route_name(int route);
+int fvit_conv3x3_dense_k(int32_t cin_valid);
+
+/* ---- the entry points from before the driver: each hands the driver the ONE image it is given --------------------------------------------- */
+/* the driver with weights.classic = weight, one term */
 int fvit_conv3x3_nhwc(int32_t dtype, const void* in, const void* weight, const float* bias, const void* residual,
                       void* out, int32_t B, int32_t Hi, int32_t Wi, int32_t Cin, int32_t Cout, int32_t stride,
                       int32_t act, const void* zeros, fvit_stream_t stream);
-/* The same convolution with the weights as TWO 16-bit terms (weight_terms = 2): weight is [Cout][2 * 9 * Cin] = [hi | lo] per output channel
- * (hi = round(w), lo = round(w - hi), each in [3][3][Cin] order); the lo image's K steps re-read the activation tile of the same
- * (tap, channel) step.  The conv's weights then carry ~22 bits while its maps stay 16-bit.  Used by the deploy plan for the three
- * Downsample.reduction convs (FV:435), whose weight rounding -- systematic, identical for every pixel of every image -- is 2.4e-4 / 1.7e-4 /
- * 2.1e-4 of FasterViT-0's 4.2e-4 conv-side logits error.  weight_terms = 1: fvit_conv3x3_nhwc. */
+/* the driver with weights.classic = weight, weights.terms = weight_terms */
 int fvit_conv3x3_nhwc_terms(int32_t dtype, const void* in, const void* weight, const float* bias, const void* residual,
                             void* out, int32_t B, int32_t Hi, int32_t Wi, int32_t Cin, int32_t Cout, int32_t stride,
                             int32_t act, int32_t weight_terms, const void* zeros, fvit_stream_t stream);
-
-/* ---- two-term MAPS (r05; the "precise" deploy plan, fastervit_amd/conv_runtime.py) -------------------------------------------------------
- * A conv-side stream is a pair of 16-bit channels-last planes (value = hi + lo, lo = round(v - hi): ~22 significant bits) or, in front of /
- * behind a transformer level, one fp32 map.  Why: replaying the fp32 reference with ONE 16-bit rounding at a time (tests/tools/
- * conv_precision_sim.py, faster_vit_4_224) a rounded conv OPERAND costs 2-8e-5 of logits error, a rounded STORED stream (the residual stream of
- * the ConvBlocks FV:502-512, the Downsample outputs FV:437-440, a transformer level's output map) 3-4e-4 each, the LayerNorm2d -> strided conv
- * operand 3.6e-4.  The reference keeps all of these in fp32.
- *
- * fvit_conv3x3_nhwc_px: fvit_conv3x3_nhwc_terms on such maps.
- *   in / in_lo          input planes; in_lo NULL = the input as ONE term (the hi plane is the MFMA operand).  With in_lo (needs weight_terms 2)
- *                       the contraction runs in.w_hi + in.w_lo + in_lo.w_hi (the lo.lo product dropped, relative 2^-22)
- *   residual / _lo      residual planes (lo optional), added in fp32; may alias out / out_lo (in-place update of the stream)
- *   out / out_lo        output planes: hi = round(y); lo = round(y - hi) when out_lo is given
- *   out_f32             instead of out / out_lo: the output as one fp32 map [B][Ho][Wo][Cout]
- *   act 2 uses the 1.5e-7-accurate erf GELU (the 16-bit entry points use a 5e-5 polynomial). */
+/* fvit_conv3x3_nhwc_terms with call.px = 1 and the two-term planes of the driver */
 int fvit_conv3x3_nhwc_px(int32_t dtype, const void* in, const void* in_lo, const void* weight, const float* bias, const void* residual,
                          const void* residual_lo, void* out, void* out_lo, float* out_f32, int32_t B, int32_t Hi, int32_t Wi, int32_t Cin,
                          int32_t Cout, int32_t stride, int32_t act, int32_t weight_terms, const void* zeros, fvit_stream_t stream);
-/* ---- dense K (r06): maps whose channel count is padded (FasterViT-4: 196 real channels in a 256-channel map, 392 in 448) -------------------
- * The classic entry points contract over 9 * Cin columns, pad channels included (1.31 x / 1.14 x the K steps at 196 / 392).  The *_dense forms
- * contract over the cin_valid real channels only: weight is [Cout][weight_terms][kd] with kd = fvit_conv3x3_dense_k(cin_valid) =
- * 9 * cin_valid rounded up to 64; column t * cin_valid + c holds w[co][tap t][channel c], the tail of the row is zero.  Cin stays the channel
- * STRIDE of the input map; cin_valid % 8 == 0 (a 16-byte chunk never straddles two taps).  cin_valid == Cin is the classic layout and kernel.
- * Everything else as fvit_conv3x3_nhwc_terms / fvit_conv3x3_nhwc_px.  fvit_conv3x3_dense_k returns -1 for an unsupported cin_valid. */
-int fvit_conv3x3_dense_k(int32_t cin_valid);
-/* r06: 1 when fvit_conv3x3_nhwc / _terms / _px run this shape in the PATCH form (8 x 16 output patches, the 10 x 18 halo of a 64-channel chunk staged once
- * for all nine taps and both weight terms): stride 1, Cout >= 128, a patch grid that wastes <= fvit_tune("conv_patch_max_waste_pct") of the pixels, and
- * fvit_tune("conv_patch") on (the default; max waste 10 %).  The patch form takes the CLASSIC weight layout (cin_valid == Cin): a caller that packs dense-K rows asks here first. */
+/* 1 when the driver runs this shape in the patch form, given classic rows */
 int fvit_conv3x3_patch_form(int32_t B, int32_t Hi, int32_t Wi, int32_t Cin, int32_t Cout, int32_t stride);
+/* the driver with weights.dense = weight (cin_valid < Cin) or weights.classic = weight (cin_valid == Cin) */
 int fvit_conv3x3_nhwc_dense(int32_t dtype, const void* in, const void* weight, const float* bias, const void* residual,
                             void* out, int32_t B, int32_t Hi, int32_t Wi, int32_t Cin, int32_t cin_valid, int32_t Cout, int32_t stride,
                             int32_t act, int32_t weight_terms, const void* zeros, fvit_stream_t stream);
+/* fvit_conv3x3_nhwc_dense with call.px = 1 and the two-term planes of the driver */
 int fvit_conv3x3_nhwc_px_dense(int32_t dtype, const void* in, const void* in_lo, const void* weight, const float* bias, const void* residual,
                                const void* residual_lo, void* out, void* out_lo, float* out_f32, int32_t B, int32_t Hi, int32_t Wi, int32_t Cin,
                                int32_t cin_valid, int32_t Cout, int32_t stride, int32_t act, int32_t weight_terms, const void* zeros,
                                fvit_stream_t stream);
+/* 1 when the driver takes the row-band kernel for an H x W map of 128 -> 128 channels, given band_frag (W <= 30, fvit_tune "conv_band" not 0) */
+int fvit_conv3x3_c128_band_supported(int32_t H, int32_t W);
+/* the driver with weights.band_frag = w_frag alone (Cin = Cout = 128, stride 1): the row-band kernel or FVIT_EINVAL */
+int fvit_conv3x3_c128_band(int32_t dtype, const void* in, const void* w_frag, const float* bias, const void* residual, void* out,
+                           int32_t B, int32_t H, int32_t W, int32_t act, const void* zeros, fvit_stream_t stream);
+/* the driver with weights.classic = weight alone and call.ln_w / ln_b / ln_eps (Cin = Cout = 64): the halo kernel's <ln> instance or FVIT_EINVAL */
+int fvit_conv3x3_c64_ln2d(int32_t dtype, const void* in, const void* weight, const float* bias, const void* residual, void* out,
+                          const float* ln_w, const float* ln_b, float eps, int32_t B, int32_t H, int32_t W, const void* zeros,
+                          fvit_stream_t stream);
+/* the driver with weights.band_frag = w_frag alone and call.ln_w / ln_b / ln_eps: the row-band kernel's <ln> instance or FVIT_EINVAL */
+int fvit_conv3x3_c128_band_ln2d(int32_t dtype, const void* in, const void* w_frag, const float* bias, const void* residual, void* out,
+                                const float* ln_w, const float* ln_b, float eps, int32_t B, int32_t H, int32_t W, const void* zeros,
+                                fvit_stream_t stream);
+
 /* fvit_layernorm2d_cl on a two-term map (in + in_lo; in_lo may be NULL) or an fp32 map (in_f32, then in = in_lo = NULL); the result as two
  * planes (out_lo may be NULL).  Statistics and affine in fp32 (timm LayerNorm2d, FV:432,438). */
 int fvit_layernorm2d_px(int32_t dtype, const void* in, const void* in_lo, const float* in_f32, void* out, void* out_lo, const float* weight,
@@ -543,29 +593,6 @@ int fvit_layernorm2d_px(int32_t dtype, const void* in, const void* in_lo, const 
  * faster_vit_4_224), its image rounding 1.2e-4. */
 int fvit_stem_conv3x3s2_px(int32_t dtype, const FvitMapView* in, const void* weight, const void* weight_lo, const float* bias, void* out,
                            int32_t B, int32_t Hi, int32_t Wi, fvit_stream_t stream);
-
-/* The same convolution for Cin = Cout = 128, stride 1, maps up to 30 pixels wide (level 1 of FasterViT-0: 28 x 28), one ROW BAND of an
- * image per workgroup: the band's input rows + halo go to LDS once, the weights stream from L2 into registers in MFMA fragment order.
- *   w_frag  op16 [4][36][2][64][8]: element e of lane 16 g + s of fragment (wave, step, ni) =
- *           weight[32 wave + (s >> 2) * 8 + ni * 4 + (s & 3)][step * 32 + 8 g + e], weight = the [128][3][3][128] matrix of fvit_conv3x3_nhwc
- *   zeros   >= 256 bytes of zeros.  Other arguments as fvit_conv3x3_nhwc.  fvit_conv3x3_c128_band_supported: 1 when W <= 30 (and the
- *   "conv_band" tuning knob is not 0). */
-int fvit_conv3x3_c128_band_supported(int32_t H, int32_t W);
-int fvit_conv3x3_c128_band(int32_t dtype, const void* in, const void* w_frag, const float* bias, const void* residual, void* out,
-                           int32_t B, int32_t H, int32_t W, int32_t act, const void* zeros, fvit_stream_t stream);
-
-/* The conv that ends a ConvBlock level with the following Downsample's LayerNorm2d (timm, over the channels of a pixel) in its epilogue:
- *     out = LayerNorm2d(round16(conv3x3(in) + bias + residual)) * ln_w + ln_b
- * i.e. LayerNorm2d of exactly the 16-bit map the plain kernel stores (statistics in fp32 from the rounded values, two passes), without that map's
- * round trip through HBM.  Stride 1, no activation, residual required (it may alias out); ln_w / ln_b f32 [C].
- *   fvit_conv3x3_c64_ln2d       Cin = Cout = 64, weight [64][3][3][64] (the register-stationary halo kernel of fvit_conv3x3_nhwc)
- *   fvit_conv3x3_c128_band_ln2d Cin = Cout = 128, w_frag and the W <= 30 limit of fvit_conv3x3_c128_band */
-int fvit_conv3x3_c64_ln2d(int32_t dtype, const void* in, const void* weight, const float* bias, const void* residual, void* out,
-                          const float* ln_w, const float* ln_b, float eps, int32_t B, int32_t H, int32_t W, const void* zeros,
-                          fvit_stream_t stream);
-int fvit_conv3x3_c128_band_ln2d(int32_t dtype, const void* in, const void* w_frag, const float* bias, const void* residual, void* out,
-                                const float* ln_w, const float* ln_b, float eps, int32_t B, int32_t H, int32_t W, const void* zeros,
-                                fvit_stream_t stream);
 
 /* Stem convolution of PatchEmbed (FV:458-460): 3x3, stride 2, pad 1, 3 -> 64 channels, + bias (folded BatchNorm) + ReLU.
  * in: strided view of the (B, 3, Hi, Wi) image in fp32 / fp16 / bf16 (the model's NCHW fp32 input needs no conversion);

@@ -54,6 +54,8 @@ def test_abi_version_and_struct_sizes(lib):
     assert ctypes.sizeof(_lib.FvitMlpWeights) == 9 * 8
     assert ctypes.sizeof(_lib.FvitBlockWeights) == 2 * 104 + 2 * 72 + 16 + 8
     assert ctypes.sizeof(_lib.FvitMapView) == 48
+    assert ctypes.sizeof(_lib.FvitConvWeights) == 3 * 8 + 2 * 4
+    assert ctypes.sizeof(_lib.FvitConvCall) == 11 * 8 + 4 + 8 * 4 + 4   # 4: tail padding to the pointers' alignment
 
 
 def test_attention_spad(lib):
