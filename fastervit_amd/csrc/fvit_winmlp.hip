@@ -6,7 +6,9 @@
 // Same contract as fvit_mlp_fused.  The per-row-block form of that kernel (fvit_mlp.hip: every wave 16 rows, ALL 4 MiB of weights through
 // LDS per 64 rows in lockstep) loses at this shape; unfused it is LayerNorm + fc1 GEMM + fc2 GEMM, three chip-wide launches per block and
 // stream shard.  Here (the work split of fvit_ctblk.hip / fvit_winblk.hip): a workgroup of 8 waves owns 64 rows = 4 row blocks.
-//   A  LayerNorm of the 64 rows into MFMA B-operand fragments in LDS (XN[rb][kk], 64 KiB).
+//   A  LayerNorm of the 64 rows into MFMA B-operand fragments in LDS (XN[rb][kk], 64 KiB).  The rows are read once, in the layout of the fc2 accumulator;
+//      in the 4-wave form without a layer scale they stay there (the accumulator starts from x less its 8 leading bits, which wait in 16 registers: the
+//      epilogue stores them + acc + b2 and reads nothing).
 //   per super-chunk of 256 hidden units (8 of them):
 //   B  wave w computes the 32 units of chunk 8 sc + w for ALL four row blocks (W1 slice straight from L2 through a register ring),
 //      applies bias + GELU and publishes the four H^T fragments in LDS (H[buf][w][rb], double-buffered: one barrier per super-chunk);
@@ -48,7 +50,8 @@ struct WinMlpParams {
                   // fragments), 2 = no barrier inside the main loop, 4 = GELU -> identity (bias + narrowing stay).  Always 0 in the shipped library.
 };
 
-// phase stamps of the TS (timeline) instances: 0 kernel entry, 1 first ring steps issued, 2 rows loaded, 3 LayerNorm written + barrier,
+// phase stamps of the TS (timeline) instances: 0 kernel entry, 1 first ring steps issued + fc1 bias in LDS, 2 rows loaded and their per-lane sums published (before the first
+// statistics barrier; up to r06 stamp 2 stood behind the in-wave row sum, with no barrier before it), 3 LayerNorm written + barrier,
 // 4 .. 4 + NSC - 1 end of super-chunk sc (capped at slot 13), 14 before the epilogue, 15 end
 template <bool TS>
 __device__ __forceinline__ void stamp(const WinMlpParams& p, int wave, int lane, int nw, int k) {
@@ -95,12 +98,12 @@ __device__ __forceinline__ void winmlp_body(const WinMlpParams& p, char* const s
     constexpr int SPS = F1T + F2T;                 // steps per super-chunk (8 / 4 per term)
     constexpr size_t WBYTES = (size_t)HID * C * 2; // one fragment-order image of fc1 (= of fc2)
     static_assert(SPS % DEPTH == 0, "ring slots must be static inside the super-chunk loop");
-    constexpr bool LN_EVEN = NW % NRB == 0;        // else (NRB = 5 / 6 with 8 waves): waves 0 .. NRB - 1 take one whole row block each in phase A
-    constexpr int WPR = LN_EVEN ? NW / NRB : 1;    // waves sharing a row block in the LayerNorm phase (2 / 1)
+    static_assert(CBW % 2 == 0, "a wave owns whole k steps of XN");
     constexpr int HBUF = (NRB * KK + 2 * NW * NRB) * 1024 + HID * 4 <= (winmlp_one_per_cu(NW, NRB) ? 150 : 72) * 1024 ? 2 : 1;   // H double-buffered when it fits
     constexpr int OFF_H = NRB * KK * 1024;         // XN: 64 KiB; H: HBUF x NW x NRB KiB; fc1 bias
     constexpr int OFF_B1 = OFF_H + HBUF * NW * NRB * 1024;
     static_assert(OFF_B1 + HID * 4 == winmlp_lds_bytes<CC, HID, NRB, NWV>(), "LDS layout");
+    static_assert(2 * NRB * 64 * CB * 4 <= HBUF * NW * NRB * 1024, "the row statistics of phase A fit in the H region");
     float* b1s = (float*)(smem + OFF_B1);
 
     const int tid = threadIdx.x;
@@ -147,13 +150,16 @@ __device__ __forceinline__ void winmlp_body(const WinMlpParams& p, char* const s
         __builtin_amdgcn_sched_barrier(0);
     };
 
-    // ---- phase A: LayerNorm; WPR waves share a row block: each reads the full rows and writes KK / WPR of the k steps ----
+    // ---- phase A: LayerNorm.  The rows are read ONCE, in the layout of the fc2 accumulator: wave w loads fragment cb = CBW w + q of row block rb, slot 4g + r <->
+    // channel (cb>>2)*64 + 16g + (cb&3)*4 + r, row 16 rb + s -- 64 registers, straight into acc2.  By the k-slot permutation of w_fc1_frag that fragment is slot
+    // (cb&1)*4 + r of XN[rb][cb>>1] in the SAME lane (the identity behind mlp_fused_kernel's KEEPX; tests/test_gpu_winmlp_rows_once.py), so wave w normalises and
+    // writes XN[rb][kk] for its own CBW / 2 k steps and all rb without a lane exchange.  The row statistics cross the waves through LDS (the H region is dead
+    // until the first super-chunk publishes): two-pass fp32, in the order of a lane that holds the whole row -- the image is bitwise that of the form that
+    // read the full rows per wave.  Only words that were written are read: every lane writes its sums of every row block (rows >= M are clamped copies).
     // request order (r03): fc1 bias, first ring steps, the rows -- all in flight before the first wait.  The bias goes to LDS (an ordinary load
     // inside the chunk loops would queue behind the ring's prefetches and drain it); its LDS write used to sit BEFORE the row loads were even
     // requested: one memory round trip (3.8 us at C = 512, profiles/r03_winmlp_phase_timeline.log) in front of the prologue.
     constexpr int NT = 64 * NW;
-    // (r06: NRB > NW -- four waves x 128 rows -- takes ceil(NRB / NW) passes: wave w normalises row blocks w, w + NW, ...)
-    constexpr int NPASS = LN_EVEN ? 1 : (NRB + NW - 1) / NW;
     float c1[HID / NT];
 #pragma unroll
     for (int i = 0; i < HID / NT; ++i) c1[i] = p.b1[tid + NT * i];
@@ -161,72 +167,120 @@ __device__ __forceinline__ void winmlp_body(const WinMlpParams& p, char* const s
 #pragma unroll
     for (int t = 0; t < DEPTH; ++t) issue(0, t, t);
     in_loop = true;
+    f4 acc2[CBW][NRB], lnw[CBW], lnb[CBW];
 #pragma unroll
-    for (int ps = 0; ps < NPASS; ++ps) {
-    const int ln_rb_raw = LN_EVEN ? wave / WPR : ps * NW + wave;
-    const bool ln_wave = LN_EVEN || ln_rb_raw < NRB;
-    const int ln_rb = ln_wave ? ln_rb_raw : 0, ln_part = LN_EVEN ? wave % WPR : 0;
-    f4 v[2 * KK];
-    {
-        const int row = min(row0 + ln_rb * 16 + s, p.M - 1);
-        const float* src = p.x + (size_t)row * C;
-        if (ln_wave) {
+    for (int rb = 0; rb < NRB; ++rb) {
+        const int row = min(row0 + rb * 16 + s, p.M - 1);   // clamped for the load; rows >= M are not stored
 #pragma unroll
-            for (int i = 0; i < 2 * KK; ++i) v[i] = *(const f4*)(src + (i >> 2) * 64 + g * 16 + (i & 3) * 4);   // i = 2 * kk + h2
+        for (int q = 0; q < CBW; ++q) {
+            const int cb = CBW * wave + q;
+            acc2[q][rb] = *(const f4*)(p.x + (size_t)row * C + (cb >> 2) * 64 + g * 16 + (cb & 3) * 4);
         }
+    }
+#pragma unroll
+    for (int q = 0; q < CBW; ++q) {
+        const int cb = CBW * wave + q;
+        lnw[q] = *(const f4*)(p.ln_w + (cb >> 2) * 64 + g * 16 + (cb & 3) * 4);
+        lnb[q] = *(const f4*)(p.ln_b + (cb >> 2) * 64 + g * 16 + (cb & 3) * 4);
     }
     __builtin_amdgcn_sched_barrier(0);
-    if (ps == 0) {
 #pragma unroll
-        for (int i = 0; i < HID / NT; ++i) b1s[tid + NT * i] = c1[i];
-        stamp<TS>(p, wave, lane, NWV, 1);
+    for (int i = 0; i < HID / NT; ++i) b1s[tid + NT * i] = c1[i];
+    stamp<TS>(p, wave, lane, NWV, 1);
+    // every lane publishes its CBW four-value sums per row block; every lane then adds the CB sums of ITS lane index in channel-block order 0 .. CB - 1 and
+    // reduces over the four lane groups: per value the additions, and their order, of a lane that holds the whole row
+    typedef float fq __attribute__((ext_vector_type(CBW)));
+    fq* const part = (fq*)(smem + OFF_H);   // [sum | squared deviations][row block][wave][lane]
+    float mean[NRB], rstd[NRB];
+#pragma unroll
+    for (int rb = 0; rb < NRB; ++rb) {
+        fq t;
+#pragma unroll
+        for (int q = 0; q < CBW; ++q) t[q] = (acc2[q][rb][0] + acc2[q][rb][1]) + (acc2[q][rb][2] + acc2[q][rb][3]);
+        part[(rb * NW + wave) * 64 + lane] = t;
     }
-    if (ln_wave) {
-        constexpr int KP = KK / WPR;
-        const int rb = ln_rb, part = ln_part;
+    stamp<TS>(p, wave, lane, NWV, 2);
+    __syncthreads();
+#pragma unroll
+    for (int rb = 0; rb < NRB; ++rb) {
         float sum = 0.f;
 #pragma unroll
-        for (int i = 0; i < 2 * KK; ++i) sum += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
+        for (int w = 0; w < NW; ++w) {
+            const fq t = part[(rb * NW + w) * 64 + lane];
+#pragma unroll
+            for (int q = 0; q < CBW; ++q) sum += t[q];
+        }
         sum = sum_xor32(sum_xor16(sum));
-        if (ps == 0) stamp<TS>(p, wave, lane, NWV, 2);
-        const float mean = sum / (float)C;
-        float sq = 0.f;
+        mean[rb] = sum / (float)C;
+        fq t;
 #pragma unroll
-        for (int i = 0; i < 2 * KK; ++i) {
-            const f4 d = v[i] - mean;
-            sq += (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]);
+        for (int q = 0; q < CBW; ++q) {
+            const f4 d = acc2[q][rb] - mean[rb];
+            t[q] = (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]);
         }
-        sq = sum_xor32(sum_xor16(sq));
-        const float rstd = rsqrtf(sq / (float)C + p.eps);
-#pragma unroll
-        for (int k8 = 0; k8 < KP; ++k8) {
-            v8 o;
-#pragma unroll
-            for (int h2 = 0; h2 < 2; ++h2) {
-                // wave-uniform choice of the part without dynamic register indexing
-                f4 xs = v[2 * k8 + h2];
-#pragma unroll
-                for (int pp = 1; pp < WPR; ++pp) xs = part == pp ? v[2 * (k8 + pp * KP) + h2] : xs;
-                const int kk = k8 + part * KP;
-                const int co = (kk >> 1) * 64 + g * 16 + (kk & 1) * 8 + h2 * 4;
-                const f4 w = *(const f4*)(p.ln_w + co);
-                const f4 bb = *(const f4*)(p.ln_b + co);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) o[h2 * 4 + r] = sat16<T>((xs[r] - mean) * rstd * w[r] + bb[r]);
-            }
-            *(v8*)(smem + ((rb * KK + k8 + part * KP) * 1024) + lane16) = o;
-        }
-    }
+        part[((NRB + rb) * NW + wave) * 64 + lane] = t;
     }
     __syncthreads();
+#pragma unroll
+    for (int rb = 0; rb < NRB; ++rb) {
+        float sq = 0.f;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+            const fq t = part[((NRB + rb) * NW + w) * 64 + lane];
+#pragma unroll
+            for (int q = 0; q < CBW; ++q) sq += t[q];
+        }
+        sq = sum_xor32(sum_xor16(sq));
+        rstd[rb] = rsqrtf(sq / (float)C + p.eps);
+    }
+#pragma unroll
+    for (int rb = 0; rb < NRB; ++rb) {
+#pragma unroll
+        for (int k2 = 0; k2 < CBW / 2; ++k2) {
+            v8 o;
+#pragma unroll
+            for (int h2 = 0; h2 < 2; ++h2)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    o[h2 * 4 + r] = sat16<T>((acc2[2 * k2 + h2][rb][r] - mean[rb]) * rstd[rb] * lnw[2 * k2 + h2][r] + lnb[2 * k2 + h2][r]);
+            *(v8*)(smem + ((rb * KK + (CBW / 2) * wave + k2) * 1024) + lane16) = o;
+        }
+    }
+    __syncthreads();   // XN visible; every wave is done with the statistics in the H region
     stamp<TS>(p, wave, lane, NWV, 3);
 
     const char* xn = smem + lane16;
-    f4 acc2[CBW][NRB];
+    // Where the epilogue is x + fc2 + b2 (no layer scale, no sibling partials to add first) x is never read again: it stays in the registers of the fc2
+    // accumulator.  Its leading bits wait in xh -- x rounded to 8 bits (e5m2, four values per register) -- and the accumulator starts from the remainder
+    // x - xh (exact in fp32, |x - xh| <= |x| / 8), so that the fc2 sums round at their own spacing and not hidden / 8 times at that of |x|; the epilogue
+    // stores xh + (acc + b2).  (Clamped to the finite e5m2 range first: beyond it the remainder simply carries more of x.)
+    // Which 8-bit value the hardware picks (OCP or FNUZ e5m2, its rounding) does not matter: encode and decode are both the hardware's, x - xh is taken from the
+    // DECODED value, so any finite xh gives xh + (x - xh) = x.
+    // The 8-wave forms (C = 512, 128 rows) have no 16 registers for xh -- the pipelined loop sits at 256 and spills them -- and no 32 KiB of LDS either: they
+    // start at zero and re-read x in the epilogue.
+    constexpr bool KEEPX = NSPLIT == 1 && NW == 4;
+    const bool acc_from_x = KEEPX && p.gamma == nullptr;
+    int xh[CBW][NRB];
 #pragma unroll
     for (int q = 0; q < CBW; ++q)
 #pragma unroll
-        for (int rb = 0; rb < NRB; ++rb) acc2[q][rb] = (f4){0.f, 0.f, 0.f, 0.f};
+        for (int rb = 0; rb < NRB; ++rb) {
+            if (acc_from_x) {
+                f4 c;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) c[r] = fminf(fmaxf(acc2[q][rb][r], -49152.f), 49152.f);
+                int pk = __builtin_amdgcn_cvt_pk_bf8_f32(c[0], c[1], 0, false);
+                pk = __builtin_amdgcn_cvt_pk_bf8_f32(c[2], c[3], pk, true);
+                xh[q][rb] = pk;
+                acc2[q][rb][0] -= __builtin_amdgcn_cvt_f32_bf8(pk, 0);
+                acc2[q][rb][1] -= __builtin_amdgcn_cvt_f32_bf8(pk, 1);
+                acc2[q][rb][2] -= __builtin_amdgcn_cvt_f32_bf8(pk, 2);
+                acc2[q][rb][3] -= __builtin_amdgcn_cvt_f32_bf8(pk, 3);
+            } else {
+                xh[q][rb] = 0;
+                acc2[q][rb] = (f4){0.f, 0.f, 0.f, 0.f};
+            }
+        }
 
     if constexpr (!PIPE) {
 #pragma unroll 1
@@ -442,40 +496,66 @@ __device__ __forceinline__ void winmlp_body(const WinMlpParams& p, char* const s
         }
     }
 
-    // ---- epilogue: x[row][c] += gamma * (out + b2); fragment cb = CBW w + q, slot 4g + r <-> channel (cb>>2)*64 + 16g + (cb&3)*4 + r, row rb * 16 + s ----
-    // Two passes (r03): ALL loads first, then the updates and stores.  Written as one load-update-store loop the compiler had to keep
-    // every store ahead of the next iteration's loads (they may alias): 16 dependent L2 / HBM round trips per lane, 8-12 us of a 45-76 us
-    // workgroup (phase timeline, profiles/r03_winmlp_phase_timeline.log).
-    const bool has_g = p.gamma != nullptr;
-    f4 bvq[CBW], glq[CBW], xv[NRB][CBW];
+    // ---- epilogue; fragment cb = CBW w + q, slot 4g + r <-> channel (cb>>2)*64 + 16g + (cb&3)*4 + r, row rb * 16 + s ----
+    f4 bvq[CBW];
 #pragma unroll
     for (int q = 0; q < CBW; ++q) {
         const int cb = CBW * wave + q;
-        const int c0 = (cb >> 2) * 64 + g * 16 + (cb & 3) * 4;
-        bvq[q] = *(const f4*)(p.b2 + c0);
-        glq[q] = *(const f4*)((has_g ? p.gamma : p.b2) + c0);
+        bvq[q] = *(const f4*)(p.b2 + (cb >> 2) * 64 + g * 16 + (cb & 3) * 4);
     }
+    // the addresses are those of phase A; recomputed from a row index the compiler cannot match with phase A's, or it keeps the 64-bit row pointers alive
+    // across the main loop (12 registers, spilled in the pipelined C = 512 form)
+    int row0e = row0;
+    asm volatile("" : "+s"(row0e));
+    if (acc_from_x) {
+        // the accumulator holds (x - xh) + fc2: x[row][c] = xh + (acc + b2), no load
 #pragma unroll
-    for (int rb = 0; rb < NRB; ++rb) {
-        const int row = min(row0 + rb * 16 + s, p.M - 1);   // clamped for the load; rows >= M are not stored
+        for (int rb = 0; rb < NRB; ++rb) {
+            const int row = row0e + rb * 16 + s;
+            if (row < p.M) {
+#pragma unroll
+                for (int q = 0; q < CBW; ++q) {
+                    const int cb = CBW * wave + q;
+                    const int pk = xh[q][rb];
+                    const f4 hi = {__builtin_amdgcn_cvt_f32_bf8(pk, 0), __builtin_amdgcn_cvt_f32_bf8(pk, 1), __builtin_amdgcn_cvt_f32_bf8(pk, 2),
+                                   __builtin_amdgcn_cvt_f32_bf8(pk, 3)};
+                    *(f4*)(p.x + (size_t)row * C + (cb >> 2) * 64 + g * 16 + (cb & 3) * 4) = hi + (acc2[q][rb] + bvq[q]);
+                }
+            }
+        }
+    } else {
+        // x[row][c] += gamma * (out + b2).  Two passes (r03): ALL loads first, then the updates and stores.  Written as one load-update-store loop the compiler
+        // had to keep every store ahead of the next iteration's loads (they may alias): 16 dependent L2 / HBM round trips per lane, 8-12 us of a 45-76 us
+        // workgroup (phase timeline, profiles/r03_winmlp_phase_timeline.log).
+        const bool has_g = p.gamma != nullptr;
+        f4 glq[CBW], xv[NRB][CBW];
 #pragma unroll
         for (int q = 0; q < CBW; ++q) {
             const int cb = CBW * wave + q;
-            xv[rb][q] = *(const f4*)(p.x + (size_t)row * C + (cb >> 2) * 64 + g * 16 + (cb & 3) * 4);
+            glq[q] = *(const f4*)((has_g ? p.gamma : p.b2) + (cb >> 2) * 64 + g * 16 + (cb & 3) * 4);
         }
-    }
-    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int rb = 0; rb < NRB; ++rb) {
-        const int row = row0 + rb * 16 + s;
-        if (row < p.M) {
+        for (int rb = 0; rb < NRB; ++rb) {
+            const int row = min(row0e + rb * 16 + s, p.M - 1);   // clamped for the load; rows >= M are not stored
 #pragma unroll
             for (int q = 0; q < CBW; ++q) {
                 const int cb = CBW * wave + q;
-                f4 o = xv[rb][q];
+                xv[rb][q] = *(const f4*)(p.x + (size_t)row * C + (cb >> 2) * 64 + g * 16 + (cb & 3) * 4);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int r = 0; r < 4; ++r) o[r] += (has_g ? glq[q][r] : 1.f) * (acc2[q][rb][r] + bvq[q][r]);
-                *(f4*)(p.x + (size_t)row * C + (cb >> 2) * 64 + g * 16 + (cb & 3) * 4) = o;
+        for (int rb = 0; rb < NRB; ++rb) {
+            const int row = row0e + rb * 16 + s;
+            if (row < p.M) {
+#pragma unroll
+                for (int q = 0; q < CBW; ++q) {
+                    const int cb = CBW * wave + q;
+                    f4 o = xv[rb][q];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) o[r] += (has_g ? glq[q][r] : 1.f) * (acc2[q][rb][r] + bvq[q][r]);
+                    *(f4*)(p.x + (size_t)row * C + (cb >> 2) * 64 + g * 16 + (cb & 3) * 4) = o;
+                }
             }
         }
     }
