@@ -268,6 +268,13 @@ struct BlockRoute {
     bool preadd_eligible = false;
     const float* pe_next = nullptr;   // position-embedding rows of block i + 1 for this block's fc2 epilogue, or null
     int win_blk_split = 1, win_mlp_split = 1;   // C = 512: workgroups that share a window's heads / a 64-row group's hidden units
+    // Stage boundaries (choose_stage_boundaries): set on block 0 / on the last block of a level only
+    RowMap entry_map;               // data set: the window attention kernel reads its local rows from the level's 16-bit map (no window_partition)
+    const float* entry_ct = nullptr;   // with entry_map: the fused carrier kernel reads ct_init itself (else a carrier-only copy ran in front)
+    RowMap exit_map;                // data set: the window MLP kernel writes the level's normalised 16-bit map (no window_reverse + LayerNorm2d)
+    const float* exit_ln_w = nullptr;
+    const float* exit_ln_b = nullptr;
+    float exit_eps = 0.f;
 };
 
 // The knobs that select a route, read once by every stage / block call: fvit_tune takes effect from the next call on, nothing is cached
@@ -280,6 +287,7 @@ struct RouteKnobs {
     const int win_mlp = tune_get("win_mlp", 1), win_mlp256 = tune_get("win_mlp256", 2), win_mlp_split = tune_get("win_mlp_split", 1);
     const int win_fused = tune_get("win_fused", 1), win_fused256 = tune_get("win_fused256", 0), win_blk_split = tune_get("win_blk_split", 1);
     const int ct_fused = tune_get("ct_fused", 1), pe_preadd = tune_get("pe_preadd", 1);
+    const int stage_entry_fused = tune_get("stage_entry_fused", 1), stage_exit_fused = tune_get("stage_exit_fused", 1);
 };
 
 static BlockRoute choose_route(const FvitStageDesc& d, const StageLayout& L, const FvitBlockWeights& w, const RouteKnobs& k) {
@@ -404,8 +412,10 @@ static int run_mlp(const FvitStageDesc& d, const StageLayout& L, const FvitMlpWe
             mc.counters = (int*)(ws + L.off_CNT);
             mc.nsplit = r.win_mlp_split;
         }
+        const bool exits = r.exit_map.data && b.rows == L.Mx;   // the window branch of the level's last block: the map is the output, X is not written
+        if (exits) { mc.out_map = r.exit_map; mc.out_ln_w = r.exit_ln_w; mc.out_ln_b = r.exit_ln_b; mc.out_eps = r.exit_eps; }
         FVIT_TRY(launch_winmlp(mc, st));
-        dbg_rowhash("winmlp.out", b.x, b.rows, d.C * 4, st);
+        if (!exits) dbg_rowhash("winmlp.out", b.x, b.rows, d.C * 4, st);
         return FVIT_OK;
     }
     case MlpRoute::MLP_FUSED: {
@@ -449,6 +459,67 @@ static AttnBlkCall window_attnblk_call(const FvitStageDesc& d, const StageLayout
     return ab;
 }
 
+// The fused-kernel call of the window MLP sub-block as run_mlp builds it, for the eligibility question of the stage exit
+static MlpFusedCall window_mlp_call(const FvitStageDesc& d, const StageLayout& L, const FvitMlpWeights& w, float* X) {
+    MlpFusedCall mc = mlp_fused_call(d.operand_dtype, X, (int)L.Mx, d.C, d.hidden, w.ln_w, w.ln_b, 1e-5f, w.w_fc1_frag, w.b_fc1, w.w_fc2_frag, w.b_fc2, w.gamma);
+    mc.terms = d.weight_terms;
+    return mc;
+}
+
+// row <-> pixel geometry of an unpadded level for the kernels that read / write the 16-bit map themselves
+static RowMap row_map(const FvitStageDesc& d, const StageLayout& L, const FvitMapView& m) {
+    RowMap r;
+    r.data = m.data; r.stride_b = m.stride_b; r.stride_h = m.stride_h; r.stride_w = m.stride_w; r.bf16 = m.dtype == FVIT_BF16;
+    r.S = L.S; r.ncw = L.ncw; r.ws = d.ws; r.nwx = d.Wp / d.ws; r.nw = L.nW;
+    return r;
+}
+static bool map_16bit_cl(const FvitMapView& m, int align_bytes) {   // 16-bit, channel-contiguous, every pixel aligned
+    return (m.dtype == FVIT_F16 || m.dtype == FVIT_BF16) && m.stride_c == 1 && ((uintptr_t)m.data % align_bytes) == 0 && (m.stride_b * 2) % align_bytes == 0 &&
+           (m.stride_h * 2) % align_bytes == 0 && (m.stride_w * 2) % align_bytes == 0;
+}
+
+static AttnBlkCall window_winblk_call(const FvitStageDesc& d, const StageLayout& L, const BlockRoute& r, const FvitBlockWeights& w, const FvitStageTables& t,
+                                      float* X, float* R, char* ws) {
+    AttnBlkCall ab = window_attnblk_call(d, L, w, t, X, R);
+    if (L.off_SLAB) {   // C = 512: heads of a window split over two sibling workgroups (fvit_tune "win_blk_split" = 2)
+        ab.slab = (float*)(ws + L.off_SLAB);
+        ab.counters = (int*)(ws + L.off_CNT);
+        ab.nsplit = r.win_blk_split;
+    }
+    return ab;
+}
+
+// The two ends of a level, decided once per stage call like the block routes: whether block 0 reads the level's 16-bit map itself (no window_partition pass, and
+// with the fused carrier kernel no carrier copy) and whether the last block's MLP kernel writes the normalised output map (no window_reverse + LayerNorm2d pass).
+// Both need an unpadded level without propagation and without a layer scale in any block; padded any-res levels, such levels and the chain routes keep the passes.
+static void choose_stage_boundaries(const FvitStageDesc& d, const StageLayout& L, const FvitBlockWeights* blocks, const FvitStageTables& t, const FvitMapView& in,
+                                    const float* ct_init, const FvitMapView* out, const FvitStageTail* tail, bool prop, const ReverseCall& rc,
+                                    const RouteKnobs& k, char* ws, std::vector<BlockRoute>& routes) {
+    if (d.depth <= 0 || d.H != d.Hp || d.W != d.Wp || prop) return;
+    for (int i = 0; i < d.depth; ++i)
+        if (blocks[i].attn.gamma || blocks[i].mlp.gamma || (d.hier && (blocks[i].hat_attn.gamma || blocks[i].hat_mlp.gamma))) return;
+    float* X = (float*)(ws + L.off_X);
+    float* R = (float*)(ws + L.off_R);
+    BlockRoute& first = routes[0];
+    if (k.stage_entry_fused && map_16bit_cl(in, 8) && d.C % 4 == 0 && d.weight_terms <= 2) {
+        bool ok = false;
+        if (first.window_attn == WinAttnRoute::ATTNBLK) ok = attnblk_map_source_supported(window_attnblk_call(d, L, blocks[0], t, X, R));
+        else if (first.window_attn == WinAttnRoute::WINBLK) ok = winblk_map_source_supported(window_winblk_call(d, L, first, blocks[0], t, X, R, ws));
+        if (ok) {
+            first.entry_map = row_map(d, L, in);
+            if (first.carrier == CarrierRoute::FUSED_CT) first.entry_ct = ct_init;
+        }
+    }
+    BlockRoute& last = routes[d.depth - 1];
+    if (k.stage_exit_fused && tail && tail->ln_w && out && reverse_ln_supported(rc) && last.window_mlp == MlpRoute::WINMLP &&
+        winmlp_exit_supported(window_mlp_call(d, L, blocks[d.depth - 1].mlp, X))) {
+        last.exit_map = row_map(d, L, *out);
+        last.exit_ln_w = tail->ln_w;
+        last.exit_ln_b = tail->ln_b;
+        last.exit_eps = tail->ln_eps;
+    }
+}
+
 // One block in the launch order at the top of this file, each sub-block on the kernel its route names
 static int run_block(const FvitStageDesc& d, const StageLayout& L, const BlockRoute& r, const FvitBlockWeights& w, const FvitStageTables& t,
                      char* ws, hipStream_t st) {
@@ -473,6 +544,7 @@ static int run_block(const FvitStageDesc& d, const StageLayout& L, const BlockRo
                                   ha.b_qkv_heads, ha.w_proj_frag, ha.b_proj, ha.gamma, ha.bias, L.scale, hm.ln_w, hm.ln_b, hm.w_fc1_frag, hm.b_fc1,
                                   hm.w_fc2_frag, hm.b_fc2, hm.gamma, 1e-5f);
         cb.terms = d.weight_terms;
+        if (r.entry_ct) { cb.X = r.entry_ct; cb.rowsA = L.G; cb.src_S = L.S; cb.src_ncw = L.ncw; }   // block 0: the carrier rows of X are not filled
         FVIT_TRY(launch_ctblk(cb, st));
         dbg_rowhash("ct.block", R, L.Mc, d.C * 4, st);
         break;
@@ -504,20 +576,19 @@ static int run_block(const FvitStageDesc& d, const StageLayout& L, const BlockRo
     const FvitAttnWeights& a = w.attn;
     switch (r.window_attn) {
     case WinAttnRoute::WINBLK: {
-        AttnBlkCall ab = window_attnblk_call(d, L, w, t, X, R);
-        if (L.off_SLAB) {   // C = 512: heads of a window split over two sibling workgroups (fvit_tune "win_blk_split" = 2)
-            ab.slab = (float*)(ws + L.off_SLAB);
-            ab.counters = (int*)(ws + L.off_CNT);
-            ab.nsplit = r.win_blk_split;
-        }
+        AttnBlkCall ab = window_winblk_call(d, L, r, w, t, X, R, ws);
+        ab.map = r.entry_map;
         FVIT_TRY(launch_winblk(ab, st));
         dbg_rowhash("win.winblk", X, L.Mx, d.C * 4, st);
         break;
     }
-    case WinAttnRoute::ATTNBLK:
-        FVIT_TRY(launch_attnblk(window_attnblk_call(d, L, w, t, X, R), st));
+    case WinAttnRoute::ATTNBLK: {
+        AttnBlkCall ab = window_attnblk_call(d, L, w, t, X, R);
+        ab.map = r.entry_map;
+        FVIT_TRY(launch_attnblk(ab, st));
         dbg_rowhash("win.attnblk", X, L.Mx, d.C * 4, st);
         break;
+    }
     case WinAttnRoute::LNGEMM_PREADDED: {
         // X already holds x + pos_embed: norm1 + qkv in one kernel
         LnGemmCall lg = {ln_call(d, L, a.ln_w, a.ln_b, X, L.Mx, nullptr), a.w_qkv, L.ldn, a.b_qkv, win.qkv, L.ldqkv, L.ldqkv, 0};
@@ -627,9 +698,6 @@ int fvit_hat_stage_forward_tail(const FvitStageDesc* desc, const FvitBlockWeight
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     float* X = (float*)(ws + L.off_X);
-    PartitionCall pc = {*in, d.batch, d.C, d.Hp, d.Wp, d.ws, X, L.S, L.ncw, d.hier ? ct_init : nullptr, L.ncw};
-    FVIT_TRY(launch_partition(pc, st));
-    dbg_rowhash("partition", X, L.Mx, d.C * 4, st);
     // (r03-r05 carried an opt-in ONE-launch form of a non-hierarchical C = 512 stage -- persistent per-window workgroups running the two kernel bodies alternately,
     // fvit_stage3.hip: measured -3 % in the joined launch structure, removed in r06: git history, profiles/HISTORY.md)
     const RouteKnobs knobs{};
@@ -641,12 +709,22 @@ int fvit_hat_stage_forward_tail(const FvitStageDesc* desc, const FvitBlockWeight
             routes[i + 1].window_attn = WinAttnRoute::LNGEMM_PREADDED;
         }
     }
+    const bool prop = d.hier && d.do_propagation && d.depth > 0 && blocks[d.depth - 1].last;
+    ReverseCall rc = {X, L.S, L.ncw, d.batch, d.C, d.Hp, d.Wp, d.H, d.W, d.ws, out ? *out : FvitMapView{},
+                      prop ? blocks[d.depth - 1].hat_attn.gamma : nullptr, prop ? tables->up_idx : nullptr};
+    choose_stage_boundaries(d, L, blocks, *tables, *in, ct_init, out, tail, prop, rc, knobs, ws, routes);
+    if (d.depth > 0 && routes[0].entry_map.data) {
+        // block 0 reads the map; the carrier rows of X are filled only for a carrier route that gathers them from X (the fused carrier kernel reads ct_init)
+        if (d.hier && !routes[0].entry_ct) FVIT_TRY(launch_ct_copy(X, L.S, 0, L.ncw, const_cast<float*>(ct_init), d.batch * L.nW, d.C, 1, st));
+    } else {
+        PartitionCall pc = {*in, d.batch, d.C, d.Hp, d.Wp, d.ws, X, L.S, L.ncw, d.hier ? ct_init : nullptr, L.ncw};
+        FVIT_TRY(launch_partition(pc, st));
+        dbg_rowhash("partition", X, L.Mx, d.C * 4, st);
+    }
     for (int i = 0; i < d.depth; ++i) FVIT_TRY(run_block(d, L, routes[i], blocks[i], *tables, ws, st));
+    if (d.depth > 0 && routes[d.depth - 1].exit_map.data) return FVIT_OK;   // the last MLP kernel wrote the normalised map
     if (pooled)   // the only consumer is the global average pool, which does not care about the token order: no reverse, no map
         return launch_rows_avgpool(X, tail->pool_out, d.batch, L.S, d.C, tail->pool_dtype, st);
-    const bool prop = d.hier && d.do_propagation && d.depth > 0 && blocks[d.depth - 1].last;
-    ReverseCall rc = {X, L.S, L.ncw, d.batch, d.C, d.Hp, d.Wp, d.H, d.W, d.ws, *out,
-                      prop ? blocks[d.depth - 1].hat_attn.gamma : nullptr, prop ? tables->up_idx : nullptr};
     if (tail && tail->ln_w) return launch_reverse_ln(rc, tail->ln_w, tail->ln_b, tail->ln_eps, st);
     FVIT_TRY(launch_reverse(rc, st));
     return FVIT_OK;

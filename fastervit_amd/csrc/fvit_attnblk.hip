@@ -53,6 +53,7 @@ struct AttnBlkParams {
                  // were removed in r02: runtime branches around the phases kept the compiler from scheduling across them)
     unsigned long long* ts;   // TS instance only (fvit_debug_attn_block_timeline): s_memtime stamps [workgroup][wave][16]: 0 entry, 1 first weight
                               // slice requested + rows gathered, 2 LayerNorm done, 3 .. 10 end of head 0 .. 7, 14 head loop done, 15 end
+    RowMap map;  // MAPSRC instances: the level's 16-bit map, the source of the rows with src_idx >= 0 (srcA is not read)
     int stagger; // 1: workgroup b walks the heads starting at head (b / 8) % heads (b % 8 = XCD, observed): the workgroups of an XCD
                  // stream different weight slices at any time, so a slice is fetched from the memory side once per XCD and found in
                  // L2 by the other workgroups (in lockstep they all wait on the same outstanding miss)
@@ -75,7 +76,9 @@ __device__ __forceinline__ void glds16(const void* gsrc, char* lds_dst) {
 //      (8 waves, two qkv buffers, bias from L2): buffer 0 takes the hi slice of a head, buffer 1 its lo slice -- requested at the top of the head,
 //      consumed after a third barrier by a second pass of P1 into the SAME q / k / v accumulators --, the proj region holds both proj slices and
 //      P3 runs once per term on the same O^T fragment.  Activations are rounded once, as everywhere in the x2 modes.
-template <typename T, int CC, int NRB, int NW, bool BIAS_LDS, bool DBQ = false, bool TS = false, int WT = 1>
+// MAPSRC: block 0 of a level (fvit_api.hip, "stage_entry_fused"): a local row is read from its pixel of the level's 16-bit map (p.map) and widened with (float),
+//      the value window_partition would have stored in srcA; carrier rows (src_idx < 0) still come from srcB.
+template <typename T, int CC, int NRB, int NW, bool BIAS_LDS, bool DBQ = false, bool TS = false, int WT = 1, bool MAPSRC = false>
 __global__ __launch_bounds__(64 * NW, (CC == 256 && WT == 1) ? 2 : 1) void attnblk_kernel(AttnBlkParams p) {
     static_assert(WT == 1 || (WT == 2 && DBQ && !BIAS_LDS && !TS), "two weight terms: DBQ form, bias from L2");
     typedef typename Op16<T>::v8 v8;
@@ -156,13 +159,18 @@ __global__ __launch_bounds__(64 * NW, (CC == 256 && WT == 1) ? 2 : 1) void attnb
 
     const float* src;
     const float* addp = nullptr;
+    const char* mpx = nullptr;   // MAPSRC: the row's pixel in the map, null for a carrier row
     {
         const int b = (int)(row / p.rows_per_image), pr = (int)(row - (int64_t)b * p.rows_per_image);
         if (p.src_idx) {
             const int si = p.src_idx[pr];
             src = si >= 0 ? p.srcA + ((size_t)b * p.rowsA + si) * C : p.srcB + ((size_t)b * p.rowsB + (-si - 1)) * C;
+            if constexpr (MAPSRC) {
+                if (si >= 0) mpx = rowmap_px(p.map, (int64_t)b * p.rowsA + si);
+            }
         } else {
             src = p.srcA + (size_t)row * C;
+            if constexpr (MAPSRC) mpx = rowmap_px(p.map, row);
         }
         if (p.add) {
             const int ai = p.add_idx ? p.add_idx[pr] : pr;
@@ -172,17 +180,30 @@ __global__ __launch_bounds__(64 * NW, (CC == 256 && WT == 1) ? 2 : 1) void attnb
     // GEMM k slot kk*32 + 8g + e carries input channel kch(kk, g, e) = (kk>>1)*64 + g*16 + (kk&1)*8 + e (w_qkv_frag is packed in
     // that order): the 64 values a lane gathers are then exactly the 64 output channels it owns in the proj accumulator, and
     // the residual epilogue uses them from registers instead of gathering the row a second time
+    // the row's 4-channel groups in kk / h2 order (the same 64 channels in the prologue and, without KEEPX, in the epilogue)
+    auto load_row = [&](f4 (&xr)[2 * KK]) {
+        auto co = [&](int i) { return (i >> 2) * 64 + g * 16 + ((i >> 1) & 1) * 8 + (i & 1) * 4; };   // i = 2 kk + h2
+        if constexpr (MAPSRC) {
+            if (mpx) { rowmap_load_row(xr, mpx, p.map.bf16, co); return; }
+        }
+#pragma unroll
+        for (int i = 0; i < 2 * KK; ++i) xr[i] = *(const f4*)(src + co(i));
+    };
     constexpr bool KEEPX = CC == 256;   // C = 512: 128 more VGPRs next to the 128 of the proj accumulator would spill: re-gather instead
     v8 xf[KK];
     f4 v[KK][2];
     {
         float sum = 0.f;
+        f4 xr[2 * KK];
+        if constexpr (MAPSRC) load_row(xr);
 #pragma unroll
         for (int kk = 0; kk < KK; ++kk)
 #pragma unroll
             for (int h2 = 0; h2 < 2; ++h2) {
                 const int co = (kk >> 1) * 64 + g * 16 + (kk & 1) * 8 + h2 * 4;
-                f4 t = *(const f4*)(src + co);
+                f4 t;
+                if constexpr (MAPSRC) t = xr[2 * kk + h2];
+                else t = *(const f4*)(src + co);
                 if (addp) t += *(const f4*)(addp + co);
                 v[kk][h2] = t;
                 sum += (t[0] + t[1]) + (t[2] + t[3]);
@@ -408,6 +429,8 @@ __global__ __launch_bounds__(64 * NW, (CC == 256 && WT == 1) ? 2 : 1) void attnb
     // ---- epilogue: x_out[row] = x_in + gamma * (out + bproj); fragment cb, slot 4g + r <-> channel (cb>>2)*64 + 16g + (cb&3)*4 + r ----
     if (row_ok) {
         float* px = p.x_out + (size_t)row * C;
+        f4 xr[2 * KK];
+        if constexpr (MAPSRC && !KEEPX) load_row(xr);
 #pragma unroll
         for (int cg = 0; cg < CB / 4; ++cg) {
             const int c0 = cg * 64 + g * 16;
@@ -417,7 +440,8 @@ __global__ __launch_bounds__(64 * NW, (CC == 256 && WT == 1) ? 2 : 1) void attnb
                 if (KEEPX) {
                     xv = v[2 * cg + (q >> 1)][q & 1];   // channel c0 + 4q = kch(2cg + (q>>1), g, 4(q&1)): the gathered row, still in registers
                 } else {
-                    xv = *(const f4*)(src + c0 + q * 4);
+                    if constexpr (MAPSRC) xv = xr[2 * (2 * cg + (q >> 1)) + (q & 1)];   // channel c0 + 4q = kch(2cg + (q>>1), g, 4(q&1))
+                    else xv = *(const f4*)(src + c0 + q * 4);
                     if (addp) xv += *(const f4*)(addp + c0 + q * 4);
                 }
                 const f4 bv = *(const f4*)(bps + c0 + q * 4);
@@ -442,6 +466,12 @@ bool attnblk_supported(int C, int heads, int S) {
     return C == 512 && heads == 16 && S > 48 && S <= 64;   // stage 3 of FasterViT-0: 7x7 windows, no carrier tokens
 }
 
+// The map-source instances exist for the forms the stage driver launches by default on 49..64-token windows at C = 256: 4 waves per window with one weight
+// term (not the fvit_tune "ab_variant" forms), 8 waves per two windows with two
+bool attnblk_map_source_supported(const AttnBlkCall& c) {
+    return c.C == 256 && c.heads == 8 && c.S > 48 && c.S <= 64 && !c.ts && (c.terms == 2 || (c.terms == 1 && tune_get("ab_variant", 0) == 0));
+}
+
 int launch_attnblk(const AttnBlkCall& c, hipStream_t stream) {
     if (ablate_skip(8)) return FVIT_OK;
     if (!attnblk_supported(c.C, c.heads, c.S) || c.nwin <= 0 || !c.wqkv_f || !c.wproj_f || !c.x_out) {
@@ -456,9 +486,15 @@ int launch_attnblk(const AttnBlkCall& c, hipStream_t stream) {
     p.ablate = diag_knob("ab_ablate");
     p.stagger = tune_get("ab_stagger", 0);
     p.ts = (unsigned long long*)c.ts;
+    p.map = c.map;
+    const bool mapsrc = c.map.data != nullptr;
+    if (mapsrc && !attnblk_map_source_supported(c)) {
+        set_error("attn_block: no map-source instance for C=%d S=%d terms=%d in this form", c.C, c.S, c.terms);
+        return FVIT_EINVAL;
+    }
     const double rows = (double)c.nwin * c.S;
     const double flops = 2.0 * rows * c.C * 4.0 * c.C + 4.0 * c.nwin * (double)c.heads * c.S * (double)c.S * 32.0;
-    const double bytes = 8.0 * rows * c.C + 8.0 * c.C * c.C;
+    const double bytes = (mapsrc ? 6.0 : 8.0) * rows * c.C + 8.0 * c.C * c.C;   // map source: 2 bytes per element read (carrier rows: 4, not told apart here)
     ProfScope prof(FVIT_K_ATTN_FUSED, flops, bytes, stream);
     prof_note(c.C == 256 ? (c.S <= 16 ? "attnblk_kernel<256,S16>" : "attnblk_kernel<256,S64>") : "attnblk_kernel<512,S64>", c.nwin);
     const bool small = c.S <= 16;
@@ -471,7 +507,12 @@ int launch_attnblk(const AttnBlkCall& c, hipStream_t stream) {
     if (c.terms == 2) {   // [hi image | lo image] weights: the double-buffered 8-wave form with a second P1 / P3 pass per head
         prof_note("attnblk_kernel<256,S64,2 terms>", (c.nwin + 1) / 2);
         if (c.ts) { set_error("attn_block timeline: one weight term only"); return FVIT_EINVAL; }
-        if (c.dtype == FVIT_F16) hipLaunchKernelGGL((attnblk_kernel<_Float16, 256, 4, 8, false, true, false, 2>), dim3((c.nwin + 1) / 2), dim3(512), 0, stream, p);
+        if (c.dtype != FVIT_F16 && c.dtype != FVIT_BF16) { set_error("attn_block: operand dtype %d not supported", c.dtype); return FVIT_EINVAL; }
+        if (mapsrc) {
+            if (c.dtype == FVIT_F16) hipLaunchKernelGGL((attnblk_kernel<_Float16, 256, 4, 8, false, true, false, 2, true>), dim3((c.nwin + 1) / 2), dim3(512), 0, stream, p);
+            else hipLaunchKernelGGL((attnblk_kernel<__bf16, 256, 4, 8, false, true, false, 2, true>), dim3((c.nwin + 1) / 2), dim3(512), 0, stream, p);
+        }
+        else if (c.dtype == FVIT_F16) hipLaunchKernelGGL((attnblk_kernel<_Float16, 256, 4, 8, false, true, false, 2>), dim3((c.nwin + 1) / 2), dim3(512), 0, stream, p);
         else if (c.dtype == FVIT_BF16) hipLaunchKernelGGL((attnblk_kernel<__bf16, 256, 4, 8, false, true, false, 2>), dim3((c.nwin + 1) / 2), dim3(512), 0, stream, p);
         else { set_error("attn_block: operand dtype %d not supported", c.dtype); return FVIT_EINVAL; }
         return check_launch("attnblk_kernel");
@@ -493,7 +534,11 @@ int launch_attnblk(const AttnBlkCall& c, hipStream_t stream) {
         hipLaunchKernelGGL((attnblk_kernel<_Float16, 256, 4, 4, false, false, true>), dim3(c.nwin), dim3(256), 0, stream, p);
         return check_launch("attnblk_kernel");
     }
-    if (c.dtype == FVIT_F16) {
+    if (mapsrc) {   // attnblk_map_source_supported: the default form
+        if (c.dtype == FVIT_F16) hipLaunchKernelGGL((attnblk_kernel<_Float16, 256, 4, 4, false, false, false, 1, true>), dim3(c.nwin), dim3(256), 0, stream, p);
+        else if (c.dtype == FVIT_BF16) hipLaunchKernelGGL((attnblk_kernel<__bf16, 256, 4, 4, false, false, false, 1, true>), dim3(c.nwin), dim3(256), 0, stream, p);
+        else { set_error("attn_block: operand dtype %d not supported", c.dtype); return FVIT_EINVAL; }
+    } else if (c.dtype == FVIT_F16) {
         if (small) FVIT_AB(_Float16, 1, 8, true);
         else if (dbq) FVIT_AB_DBQ(_Float16);
         else if (variant == 1) FVIT_AB(_Float16, 4, 8, true);

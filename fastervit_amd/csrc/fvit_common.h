@@ -97,6 +97,68 @@ __device__ __forceinline__ float group_max(float x) {
     return x;
 }
 
+// Stage-boundary fusion (fvit_api.hip: "stage_entry_fused" / "stage_exit_fused"): a level's 16-bit channels-last map as the row source of the
+// block-0 attention kernel, or as the destination of the last MLP kernel, in place of the window_partition / window_reverse passes.
+// Unpadded maps only (H == Hp, W == Wp).  data == nullptr: not used.
+struct RowMap {
+    void* data = nullptr;
+    int64_t stride_b = 0, stride_h = 0, stride_w = 0;   // in elements; the channel stride is 1
+    int bf16 = 0;                                       // element type: 0 fp16, 1 bf16
+    int S = 0, ncw = 0;                                 // rows per window, carrier rows in front of a window's local rows
+    int ws = 0, nwx = 0, nw = 0;                        // window side, windows per row of windows, windows per image
+};
+// token_row of fvit_rows.hip inverted: element offset of the pixel behind row `row` of the window tensor; a carrier row gives -1
+__device__ __forceinline__ int64_t rowmap_pixel(const RowMap& m, int64_t row) {
+    const int64_t win = row / m.S;
+    const int tok = (int)(row - win * m.S) - m.ncw;
+    if (tok < 0) return -1;
+    const int b = (int)(win / m.nw), wi = (int)(win - (int64_t)b * m.nw);
+    const int wy = wi / m.nwx, wx = wi - wy * m.nwx, ty = tok / m.ws, tx = tok - ty * m.ws;
+    return b * m.stride_b + (wy * m.ws + ty) * m.stride_h + (wx * m.ws + tx) * m.stride_w;
+}
+// the pixel's address, or null for a row that has no pixel (the caller then reads its fp32 row source)
+__device__ __forceinline__ const char* rowmap_px(const RowMap& m, int64_t row) {
+    const int64_t off = rowmap_pixel(m, row);
+    return off >= 0 ? (const char*)m.data + 2 * off : nullptr;
+}
+// four channels of a map pixel (V4 = h4 / b4, 8-byte aligned) widened to fp32: the value window_partition stores
+template <typename V4>
+__device__ __forceinline__ f4 rowmap_load4(const void* px) {
+    const V4 v = *(const V4*)px;
+    f4 t;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) t[r] = (float)v[r];
+    return t;
+}
+// N groups of four channels, group i at channel off(i): ONE branch on the map's element type around the whole batch of loads
+template <int N, typename OFF>
+__device__ __forceinline__ void rowmap_load_row(f4 (&v)[N], const char* px, int bf16, OFF off) {
+    if (bf16) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) v[i] = rowmap_load4<b4>(px + 2 * off(i));
+    } else {
+#pragma unroll
+        for (int i = 0; i < N; ++i) v[i] = rowmap_load4<h4>(px + 2 * off(i));
+    }
+}
+// x rounded to the map type, as fp32: the value window_reverse stores
+__device__ __forceinline__ float rowmap_round(float x, int bf16) { return bf16 ? (float)(__bf16)x : (float)(_Float16)x; }
+
+// eight channels narrowed to the map type and stored at a pixel (16-byte aligned)
+__device__ __forceinline__ void rowmap_store8(void* px, const float (&y)[8], int bf16) {
+    if (bf16) {
+        b8 o;
+#pragma unroll
+        for (int r = 0; r < 8; ++r) o[r] = (__bf16)y[r];
+        *(b8*)px = o;
+    } else {
+        h8 o;
+#pragma unroll
+        for (int r = 0; r < 8; ++r) o[r] = (_Float16)y[r];
+        *(h8*)px = o;
+    }
+}
+
 // erf with |error| <= 1.5e-7 (Abramowitz & Stegun 7.1.26): far below the 16-bit rounding of any GELU
 // output here, branch-free and much cheaper than libm erff inside fused epilogues.
 __device__ __forceinline__ float fast_erf(float x) {
@@ -357,7 +419,14 @@ struct MlpFusedCall {
     int* counters = nullptr;   // int32 [ceil(M / 64)], zero before the first launch (the kernel leaves them zero)
     int nsplit = 1;
     void* ts = nullptr;        // diagnosis (fvit_debug_win_mlp_timeline): u64 [workgroups][waves][16] phase stamps
+    // stage exit (winmlp_exit_supported): the epilogue rounds x + fc2 to the map type, normalises it over C (LayerNorm2d: out_ln_w / out_ln_b / out_eps)
+    // and stores the local rows at their pixels of out_map; x is not written
+    RowMap out_map;
+    const float* out_ln_w = nullptr;
+    const float* out_ln_b = nullptr;
+    float out_eps = 0.f;
 };
+bool winmlp_exit_supported(const MlpFusedCall& c);   // the 4-wave C = 256 form without a layer scale, one or two weight terms
 size_t winmlp_split_slab_bytes(int64_t M, int C, int nsplit);
 bool mlp_fused_supported(int C, int hidden);
 int launch_mlp_fused(const MlpFusedCall& c, hipStream_t stream);
@@ -395,8 +464,11 @@ struct AttnBlkCall {
     int nsplit = 1;
     int terms = 1;             // weight terms of the fragment arrays (fvit_winblk.hip, C = 512: 1 or 2; fvit_attnblk.hip: 1)
     void* ts = nullptr;        // fvit_attnblk.hip: stamp buffer of the timeline instance (fvit_debug_attn_block_timeline)
+    RowMap map;                // stage entry (*_map_source_supported): rows with src_idx >= 0 (all rows without src_idx) come from this map, srcA is not read
 };
 bool attnblk_supported(int C, int heads, int S);
+bool attnblk_map_source_supported(const AttnBlkCall& c);   // the default C = 256 window forms (one or two weight terms)
+bool winblk_map_source_supported(const AttnBlkCall& c);    // every form but the split-heads one
 int launch_attnblk(const AttnBlkCall& c, hipStream_t stream);
 // r06: the same contract for C = 256 / 8 heads / 49..64-token windows with a wave per (window, head) (fvit_attnblk2.hip); launch_attnblk dispatches to it
 bool attnblk2_supported(int C, int heads, int S);
@@ -462,6 +534,8 @@ struct CtBlkCall {
     float eps;
     int terms = 1;   // weight terms of the four fragment arrays (1 or 2)
     void* ts = nullptr;   // stamp buffer of the timeline instance (fvit_debug_ct_block_timeline)
+    int src_S = 0, src_ncw = 0;   // stage entry, src_S > 0: X is ct_init (rowsA = G rows per image, windowed order); row src_idx of the window tensor is its
+                                  // row (src_idx / src_S) * src_ncw + src_idx % src_S
 };
 bool ctblk_supported(int C, int heads, int G, int hidden);
 int launch_ctblk(const CtBlkCall& c, hipStream_t stream);

@@ -30,6 +30,8 @@ struct CtBlkParams {
     const float* add;        // hat_pos_embed rows [G][C] or null
     float* R;                // out [B * G][C]
     int rowsA, B, G;
+    int src_S, src_ncw;      // src_S > 0 (block 0 of a level, "stage_entry_fused"): X is ct_init [B * G][C] in windowed order and row si of the window tensor is
+                             // its row (si / src_S) * src_ncw + si % src_S -- the carrier slots of the window tensor are not read
     const float* ln1_w; const float* ln1_b;
     const void* wqkv_f;      // op16 [heads][6][C/32][64][8]
     const float* bqkv;       // f32  [heads][96]
@@ -46,6 +48,12 @@ struct CtBlkParams {
     int touch;
     unsigned long long* ts;   // ctblk8_kernel TS instance (fvit_debug_ct_block_timeline): s_memtime stamps [image][wave][16]
 };
+
+// row of p.X (inside the image) that holds carrier token tok
+__device__ __forceinline__ int ct_src_row(const CtBlkParams& p, int tok) {
+    const int si = p.src_idx[tok];
+    return p.src_S > 0 ? (si / p.src_S) * p.src_ncw + si % p.src_S : si;
+}
 
 // DEPTH: steps of the register ring in flight; MINB: workgroups per CU the register budget is sized for (1: one wave per SIMD, 512
 // registers, the ring and every phase's operands fit without scratch; 2: 256 registers, other kernels' waves can share the SIMD)
@@ -142,7 +150,7 @@ __global__ __launch_bounds__(256, MINB) void ctblk_kernel(CtBlkParams p) {
     }
 
     // ---- gather (+ position embedding) and LayerNorm: lane (g, s) holds token s, channels (cb>>2)*64 + 16g + (cb&3)*4 .. +3 in v[cb] ----
-    const float* src = p.X + ((size_t)img * p.rowsA + p.src_idx[tok]) * C + g * 16;
+    const float* src = p.X + ((size_t)img * p.rowsA + ct_src_row(p, tok)) * C + g * 16;
     // optional inputs are read through a valid stand-in pointer and masked with a scalar select: a branch per load splits the phase into
     // basic blocks and the partial sums spill across them
     const bool has_add = p.add != nullptr, has_g1 = p.gamma1 != nullptr, has_g2 = p.gamma2 != nullptr;
@@ -462,7 +470,7 @@ __global__ __launch_bounds__(512, 1) void ctblk8_kernel(CtBlkParams p) {
 #pragma unroll
     for (int im = 0; im < NIMG; ++im) {
         const int img = min(img0 + im, p.B - 1);
-        const float* src = p.X + ((size_t)img * p.rowsA + p.src_idx[tok]) * C + g * 16;
+        const float* src = p.X + ((size_t)img * p.rowsA + ct_src_row(p, tok)) * C + g * 16;
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const int cb = 2 * wave + q;
@@ -838,6 +846,7 @@ int launch_ctblk(const CtBlkCall& c, hipStream_t stream) {
     }
     CtBlkParams p;
     p.X = c.X; p.src_idx = c.src_idx; p.add = c.add; p.R = c.R; p.rowsA = c.rowsA; p.B = c.batch; p.G = c.G;
+    p.src_S = c.src_S; p.src_ncw = c.src_ncw;
     p.ln1_w = c.ln1_w; p.ln1_b = c.ln1_b; p.wqkv_f = c.wqkv_f; p.bqkv = c.bqkv; p.wproj_f = c.wproj_f; p.bproj = c.bproj; p.gamma1 = c.gamma1;
     p.bias = c.bias; p.scale = c.scale;
     p.ln2_w = c.ln2_w; p.ln2_b = c.ln2_b; p.w1f = c.w1f; p.b1 = c.b1; p.w2f = c.w2f; p.b2 = c.b2; p.gamma2 = c.gamma2; p.eps = c.eps;

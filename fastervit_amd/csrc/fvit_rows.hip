@@ -624,6 +624,7 @@ int launch_ct_copy(float* x, int rows_per_win, int row_off, int ncw, float* ct, 
     const int C4 = C / 4;
     const int64_t n = nrows * C4;
     ProfScope prof(FVIT_K_OTHER, 0.0, 8.0 * nrows * C, stream);
+    prof_note("ct_rows_kernel", (int)((n + 255) / 256));
     hipLaunchKernelGGL(ct_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, x, ct, rows_per_win, row_off, ncw,
                        nrows, C4, to_x);
     return check_launch("ct_rows_kernel");

@@ -51,6 +51,7 @@ struct WinBlkParams {
     float scale;
     float* slab;     // NSPLIT > 1: f32 partial outputs [window][NSPLIT][waves][16][64 lanes][4] (64 x C x 4 bytes per (window, split))
     int* counters;   // NSPLIT > 1: one arrival counter per window, zero before the launch, zero again after it
+    RowMap map;      // MAPSRC instances: the level's 16-bit map, the source of the rows with src_idx >= 0 (srcA is not read)
 };
 
 // CC = 512: 8 waves, one workgroup per CU.  CC = 256 (stage 2, 8 heads): 4 waves (two heads and four channel blocks each, like the 8-wave
@@ -61,12 +62,14 @@ struct WinBlkParams {
 // ticket; the last arriver acquires, adds the partials in split order and applies the residual; nobody waits).
 // WT = 2 (r03): two-term weights (hi + lo 16-bit images, the lo image after the hi image in the fragment arrays): the qkv and proj k loops run
 // twice over the same activation fragments, once per weight image -- same registers and LDS, twice the weight stream.
+// MAPSRC: block 0 of a level (fvit_api.hip, "stage_entry_fused"): a local row is read -- in phase A and again in the epilogue -- from its pixel of the level's
+// 16-bit map (p.map) and widened with (float), the value window_partition would have stored in srcA; carrier rows (src_idx < 0) still come from srcB.
 // LDS bytes of a workgroup: XN (4 row blocks x C / 32 k steps), O^T (4 x heads of this workgroup), the qkv bias copy
 template <int CC, int NSPLIT>
 constexpr int winblk_lds_bytes() { return 4 * (CC / 32) * 1024 + 4 * (CC / 32 / NSPLIT) * 1024 + (CC / 32) * 96 * 4; }
 
 // The kernel body as a device function (blk = blockIdx.x of a stand-alone launch): fvit_stage3.hip runs it as one phase of a persistent workgroup.
-template <typename T, int CC, int NWV, int NSPLIT = 1, int WT = 1>
+template <typename T, int CC, int NWV, int NSPLIT = 1, int WT = 1, bool MAPSRC = false>
 __device__ __forceinline__ void winblk_body(const WinBlkParams& p, char* const smem, const int blk) {
     typedef typename Op16<T>::v8 v8;
     constexpr int C = CC, KK = C / 32, CB = C / 16, HEADS = C / 32, NW = NWV, NRB = 4, SP = 64;
@@ -145,21 +148,36 @@ __device__ __forceinline__ void winblk_body(const WinBlkParams& p, char* const s
         const int64_t row = (int64_t)win * p.S + (tok < p.S ? tok : p.S - 1);   // clamped: always a real row
         const int b = (int)(row / p.rows_per_image), pr = (int)(row - (int64_t)b * p.rows_per_image);
         const float* src;
+        const char* mpx = nullptr;   // MAPSRC: the row's pixel in the map, null for a carrier row
         if (p.src_idx) {
             const int si = p.src_idx[pr];
             src = si >= 0 ? p.srcA + ((size_t)b * p.rowsA + si) * C : p.srcB + ((size_t)b * p.rowsB + (-si - 1)) * C;
+            if constexpr (MAPSRC) {
+                if (si >= 0) mpx = rowmap_px(p.map, (int64_t)b * p.rowsA + si);
+            }
         } else {
             src = p.srcA + (size_t)row * C;
+            if constexpr (MAPSRC) mpx = rowmap_px(p.map, row);
         }
         const int ai = p.add ? (p.add_idx ? p.add_idx[pr] : pr) : -1;
         const bool has_add = ai >= 0;
         const float* addp = has_add ? p.add + (size_t)ai * C : src;
         f4 v[2 * KK];
         float sum = 0.f;
+        if constexpr (MAPSRC) {   // one branch per row, not per load: the loads of a row stay one batch
+            if (mpx) {
+                rowmap_load_row(v, mpx, p.map.bf16, [&](int i) { return (i >> 2) * 64 + g * 16 + (i & 3) * 4; });
+            } else {
+#pragma unroll
+                for (int i = 0; i < 2 * KK; ++i) v[i] = *(const f4*)(src + (i >> 2) * 64 + g * 16 + (i & 3) * 4);
+            }
+        }
 #pragma unroll
         for (int i = 0; i < 2 * KK; ++i) {
             const int co = (i >> 2) * 64 + g * 16 + (i & 3) * 4;   // i = 2 * kk + h2
-            f4 t = *(const f4*)(src + co);
+            f4 t;
+            if constexpr (MAPSRC) t = v[i];
+            else t = *(const f4*)(src + co);
             const f4 a = *(const f4*)(addp + co);
 #pragma unroll
             for (int r = 0; r < 4; ++r) t[r] += has_add ? a[r] : 0.f;
@@ -376,17 +394,28 @@ __device__ __forceinline__ void winblk_body(const WinBlkParams& p, char* const s
             const int64_t row = (int64_t)win * p.S + tok;
             const int b = (int)(row / p.rows_per_image), pr = (int)(row - (int64_t)b * p.rows_per_image);
             const float* src;
+            const char* mpx = nullptr;
             if (p.src_idx) {
                 const int si = p.src_idx[pr];
                 src = si >= 0 ? p.srcA + ((size_t)b * p.rowsA + si) * C : p.srcB + ((size_t)b * p.rowsB + (-si - 1)) * C;
+                if constexpr (MAPSRC) {
+                    if (si >= 0) mpx = rowmap_px(p.map, (int64_t)b * p.rowsA + si);
+                }
             } else {
                 src = p.srcA + (size_t)row * C;
+                if constexpr (MAPSRC) mpx = rowmap_px(p.map, row);
             }
             const int ai = p.add ? (p.add_idx ? p.add_idx[pr] : pr) : -1;
             float* px = p.x_out + (size_t)row * C + c0;
+            f4 xm[4];
+            if constexpr (MAPSRC) {
+                if (mpx) rowmap_load_row(xm, mpx, p.map.bf16, [&](int q) { return c0 + q * 4; });
+            }
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                f4 xv = *(const f4*)(src + c0 + q * 4);
+                f4 xv;
+                if (MAPSRC && mpx) xv = xm[q];
+                else xv = *(const f4*)(src + c0 + q * 4);
                 if (ai >= 0) xv += *(const f4*)(p.add + (size_t)ai * C + c0 + q * 4);
                 const f4 bv = *(const f4*)(p.bproj + c0 + q * 4);
                 const f4 gl = *(const f4*)((has_g ? p.gamma : p.bproj) + c0 + q * 4);
@@ -398,10 +427,10 @@ __device__ __forceinline__ void winblk_body(const WinBlkParams& p, char* const s
     }
 }
 
-template <typename T, int CC, int NWV, int NSPLIT = 1, int WT = 1>
+template <typename T, int CC, int NWV, int NSPLIT = 1, int WT = 1, bool MAPSRC = false>
 __global__ __launch_bounds__(64 * NWV, NWV == 8 ? 1 : 2) void winblk_kernel(WinBlkParams p) {
     __shared__ __attribute__((aligned(16))) char smem[winblk_lds_bytes<CC, NSPLIT>()];
-    winblk_body<T, CC, NWV, NSPLIT, WT>(p, smem, blockIdx.x);
+    winblk_body<T, CC, NWV, NSPLIT, WT, MAPSRC>(p, smem, blockIdx.x);
 }
 
 inline WinBlkParams make_winblk_params(const AttnBlkCall& c) {
@@ -411,6 +440,7 @@ inline WinBlkParams make_winblk_params(const AttnBlkCall& c) {
     p.wqkv_f = c.wqkv_f; p.bqkv = c.bqkv; p.wproj_f = c.wproj_f; p.bproj = c.bproj; p.gamma = c.gamma; p.bias = c.bias; p.x_out = c.x_out;
     p.nwin = c.nwin; p.S = c.S; p.scale = c.scale;
     p.slab = c.slab; p.counters = c.counters;
+    p.map = c.map;
     return p;
 }
 
@@ -418,6 +448,12 @@ inline WinBlkParams make_winblk_params(const AttnBlkCall& c) {
 
 #ifndef FVIT_BODIES_ONLY
 bool winblk_supported(int C, int heads, int S) { return ((C == 512 && heads == 16) || (C == 256 && heads == 8)) && S > 48 && S <= 64; }
+
+// The map-source instances: C = 512 with one or two weight terms and C = 256; not the split-heads form (fvit_tune "win_blk_split" = 2)
+bool winblk_map_source_supported(const AttnBlkCall& c) {
+    const bool split = c.C == 512 && c.terms == 1 && c.nsplit == 2 && c.slab && c.counters;
+    return winblk_supported(c.C, c.heads, c.S) && !split && (c.terms == 1 || (c.terms == 2 && c.C == 512));
+}
 
 int launch_winblk(const AttnBlkCall& c, hipStream_t stream) {
     if (!winblk_supported(c.C, c.heads, c.S) || c.nwin <= 0 || !c.wqkv_f || !c.wproj_f || !c.x_out || !c.bias || !c.bqkv) {
@@ -433,12 +469,24 @@ int launch_winblk(const AttnBlkCall& c, hipStream_t stream) {
     const bool split = c.C == 512 && c.terms == 1 && c.nsplit == 2 && c.slab && c.counters;
     const double rows = (double)c.nwin * c.S;
     const double flops = rows * (2.0 * c.C * 3 * c.C + 4.0 * c.S * c.C + 2.0 * c.C * c.C);
-    const double bytes = rows * c.C * 8.0 + c.terms * 2.0 * 4.0 * c.C * c.C;
+    const bool mapsrc = c.map.data != nullptr;
+    if (mapsrc && !winblk_map_source_supported(c)) {
+        set_error("win_block: no map-source instance for C=%d terms=%d nsplit=%d", c.C, c.terms, c.nsplit);
+        return FVIT_EINVAL;
+    }
+    const double bytes = rows * c.C * (mapsrc ? 6.0 : 8.0) + c.terms * 2.0 * 4.0 * c.C * c.C;   // map source: 2 bytes per element read
     ProfScope prof(FVIT_K_ATTN_FUSED, flops, bytes, stream);
     const int grid = split ? (c.nwin + 7) / 8 * 8 * 2 : c.nwin;
     prof_note(c.C == 512 ? (split ? "winblk_kernel<512,S64,split2>" : "winblk_kernel<512,S64>") : "winblk_kernel<256,S64>", grid);
     if (c.dtype != FVIT_F16 && c.dtype != FVIT_BF16) { set_error("win_block: operand dtype %d not supported", c.dtype); return FVIT_EINVAL; }
-    if (c.terms == 2) {
+    if (mapsrc) {
+#define FVIT_WB_MAP(T_) do { \
+        if (c.terms == 2) hipLaunchKernelGGL((winblk_kernel<T_, 512, 8, 1, 2, true>), dim3(c.nwin), dim3(512), 0, stream, p); \
+        else if (c.C == 512) hipLaunchKernelGGL((winblk_kernel<T_, 512, 8, 1, 1, true>), dim3(c.nwin), dim3(512), 0, stream, p); \
+        else hipLaunchKernelGGL((winblk_kernel<T_, 256, 4, 1, 1, true>), dim3(c.nwin), dim3(256), 0, stream, p); } while (0)
+        if (c.dtype == FVIT_F16) FVIT_WB_MAP(_Float16); else FVIT_WB_MAP(__bf16);
+#undef FVIT_WB_MAP
+    } else if (c.terms == 2) {
         if (c.dtype == FVIT_F16) hipLaunchKernelGGL((winblk_kernel<_Float16, 512, 8, 1, 2>), dim3(c.nwin), dim3(512), 0, stream, p);
         else hipLaunchKernelGGL((winblk_kernel<__bf16, 512, 8, 1, 2>), dim3(c.nwin), dim3(512), 0, stream, p);
     } else if (split) {

@@ -46,6 +46,10 @@ struct WinMlpParams {
     float* slab;     // NSPLIT > 1: f32 partial outputs [row group][NSPLIT][waves][CBW * NRB][64 lanes][4], 64 x C x 4 bytes per (row group, split)
     int* counters;   // NSPLIT > 1: one arrival counter per row group, zero before the launch, zero again after it
     unsigned long long* ts;   // TS instances only (fvit_debug_win_mlp_timeline): s_memtime stamps [workgroup][wave][16]
+    RowMap out_map;           // LNMAP instances: the level's 16-bit output map
+    const float* out_ln_w;    // ... and the LayerNorm2d that follows the level (weight, bias, eps)
+    const float* out_ln_b;
+    float out_eps;
     int ablate;   // DIAGNOSIS build only (fvit_tune "wm_ablate", results are wrong): 1 = no weight loads inside the main loop (the ring keeps the first steps'
                   // fragments), 2 = no barrier inside the main loop, 4 = GELU -> identity (bias + narrowing stay).  Always 0 in the shipped library.
 };
@@ -73,6 +77,10 @@ __device__ __forceinline__ void stamp(const WinMlpParams& p, int wave, int lane,
 // split 0, 1, .. (bitwise repeatable whoever arrives last), applies bias / gamma / residual and resets the counter.  Nobody waits for
 // anybody (no spin: placement- and residency-independent).  Sibling workgroups get block ids that differ by a multiple of 8 (same XCD
 // under the observed round-robin dispatch): their partials and the rows they all read stay in one L2 (speed only, never correctness).
+// LNMAP (the last block of a level, fvit_api.hip "stage_exit_fused"; the 4-wave form with the residual kept in registers): the epilogue writes the level's
+// normalised 16-bit map instead of x.  v = x + fc2 + b2 is rounded to the map type -- the value window_reverse stores --, LayerNorm2d statistics over the C
+// channels are taken from the rounded values in fp32, two passes (in-lane over the lane's 16 channels, the row swaps over the four lane groups, LDS over the
+// four waves, each in a fixed order), and (v - mean) rstd w + b goes to the row's pixel.  Carrier rows and rows >= M are not stored; x is not written.
 // LDS bytes of a workgroup: XN (NRB x C / 32 KiB), H (single or double buffered, see HBUF below), the fc1 bias
 // one workgroup per CU (all of its LDS, one or two waves per SIMD): the 8-wave forms, and (r06 experiment) 4 waves x 128 rows with up to 512 registers per wave
 constexpr bool winmlp_one_per_cu(int NWV, int NRB) { return NWV == 8 || NRB == 8; }
@@ -84,7 +92,7 @@ constexpr int winmlp_lds_bytes() {
 
 // The kernel body as a device function (blk = blockIdx.x of a stand-alone launch): fvit_stage3.hip runs it as one phase of a persistent workgroup
 // (the timeline stamps index by blockIdx.x: stand-alone launches only).
-template <typename T, int CC, int HID, int NRB, int DEPTH, int NWV = 8, int SP = 1, int NSPLIT = 1, bool TS = false, bool PIPE = false>
+template <typename T, int CC, int HID, int NRB, int DEPTH, int NWV = 8, int SP = 1, int NSPLIT = 1, bool TS = false, bool PIPE = false, bool LNMAP = false>
 __device__ __forceinline__ void winmlp_body(const WinMlpParams& p, char* const smem, const int blk) {
     typedef typename Op16<T>::v8 v8;
     constexpr int C = CC, KK = C / 32, CB = C / 16, NW = NWV;
@@ -507,7 +515,79 @@ __device__ __forceinline__ void winmlp_body(const WinMlpParams& p, char* const s
     // across the main loop (12 registers, spilled in the pipelined C = 512 form)
     int row0e = row0;
     asm volatile("" : "+s"(row0e));
-    if (acc_from_x) {
+    if constexpr (LNMAP) {
+        static_assert(KEEPX && CBW == 4 && HBUF == 2 && !PIPE && !TS, "the stage-exit epilogue: 4 waves x 16 contiguous channels per lane, plain loop, double-buffered H");
+        // (launch_winmlp admits no layer scale here: acc_from_x holds, the accumulator is (x - xh) + fc2)
+        const int mb = p.out_map.bf16;
+        // the H buffer the last super-chunk did not use: its last readers passed that super-chunk's barrier before any wave got here
+        float* const st = (float*)(smem + OFF_H + (((NSC - 1) & 1) ^ 1) * NW * NRB * 1024);   // [sum | squared deviations][row block][wave][16 rows]
+#pragma unroll
+        for (int rb = 0; rb < NRB; ++rb) {
+            float sum = 0.f;
+#pragma unroll
+            for (int q = 0; q < CBW; ++q) {
+                const int pk = xh[q][rb];
+                const f4 hi = {__builtin_amdgcn_cvt_f32_bf8(pk, 0), __builtin_amdgcn_cvt_f32_bf8(pk, 1), __builtin_amdgcn_cvt_f32_bf8(pk, 2),
+                               __builtin_amdgcn_cvt_f32_bf8(pk, 3)};
+                const f4 v = hi + (acc2[q][rb] + bvq[q]);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) acc2[q][rb][r] = rowmap_round(v[r], mb);
+                sum += (acc2[q][rb][0] + acc2[q][rb][1]) + (acc2[q][rb][2] + acc2[q][rb][3]);
+            }
+            sum = sum_xor32(sum_xor16(sum));
+            if (g == 0) st[(rb * NW + wave) * 16 + s] = sum;
+        }
+        __syncthreads();
+        float omean[NRB], orstd[NRB];
+#pragma unroll
+        for (int rb = 0; rb < NRB; ++rb) {
+            float sum = 0.f;
+#pragma unroll
+            for (int w = 0; w < NW; ++w) sum += st[(rb * NW + w) * 16 + s];
+            omean[rb] = sum / (float)C;
+            float sq = 0.f;
+#pragma unroll
+            for (int q = 0; q < CBW; ++q) {
+                const f4 d = acc2[q][rb] - omean[rb];
+                sq += (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]);
+            }
+            sq = sum_xor32(sum_xor16(sq));
+            if (g == 0) st[((NRB + rb) * NW + wave) * 16 + s] = sq;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int rb = 0; rb < NRB; ++rb) {
+            float sq = 0.f;
+#pragma unroll
+            for (int w = 0; w < NW; ++w) sq += st[((NRB + rb) * NW + w) * 16 + s];
+            orstd[rb] = rsqrtf(sq / (float)C + p.out_eps);
+        }
+        const int c0 = wave * 64 + g * 16;   // the lane's 16 channels: fragment q holds c0 + 4q .. + 3
+        f4 ow[CBW], ob[CBW];
+#pragma unroll
+        for (int q = 0; q < CBW; ++q) {
+            ow[q] = *(const f4*)(p.out_ln_w + c0 + q * 4);
+            ob[q] = *(const f4*)(p.out_ln_b + c0 + q * 4);
+        }
+#pragma unroll
+        for (int rb = 0; rb < NRB; ++rb) {
+            const int row = row0e + rb * 16 + s;
+            const int64_t off = rowmap_pixel(p.out_map, min(row, p.M - 1));
+            if (row < p.M && off >= 0) {
+                char* px = (char*)p.out_map.data + 2 * (off + c0);
+#pragma unroll
+                for (int q2 = 0; q2 < CBW / 2; ++q2) {
+                    float y[8];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        y[r] = (acc2[2 * q2][rb][r] - omean[rb]) * orstd[rb] * ow[2 * q2][r] + ob[2 * q2][r];
+                        y[4 + r] = (acc2[2 * q2 + 1][rb][r] - omean[rb]) * orstd[rb] * ow[2 * q2 + 1][r] + ob[2 * q2 + 1][r];
+                    }
+                    rowmap_store8(px + q2 * 16, y, mb);
+                }
+            }
+        }
+    } else if (acc_from_x) {
         // the accumulator holds (x - xh) + fc2: x[row][c] = xh + (acc + b2), no load
 #pragma unroll
         for (int rb = 0; rb < NRB; ++rb) {
@@ -565,16 +645,17 @@ __device__ __forceinline__ void winmlp_body(const WinMlpParams& p, char* const s
     }
 }
 
-template <typename T, int CC, int HID, int NRB, int DEPTH, int NWV = 8, int SP = 1, int NSPLIT = 1, bool TS = false, bool PIPE = false>
+template <typename T, int CC, int HID, int NRB, int DEPTH, int NWV = 8, int SP = 1, int NSPLIT = 1, bool TS = false, bool PIPE = false, bool LNMAP = false>
 __global__ __launch_bounds__(64 * NWV, winmlp_one_per_cu(NWV, NRB) ? 1 : 2) void winmlp_kernel(WinMlpParams p) {
     __shared__ __attribute__((aligned(16))) char smem[winmlp_lds_bytes<CC, HID, NRB, NWV>()];
-    winmlp_body<T, CC, HID, NRB, DEPTH, NWV, SP, NSPLIT, TS, PIPE>(p, smem, blockIdx.x);
+    winmlp_body<T, CC, HID, NRB, DEPTH, NWV, SP, NSPLIT, TS, PIPE, LNMAP>(p, smem, blockIdx.x);
 }
 
 inline WinMlpParams make_winmlp_params(const MlpFusedCall& c) {
     WinMlpParams p;
     p.x = c.x; p.ln_w = c.ln_w; p.ln_b = c.ln_b; p.w1f = c.w1f; p.b1 = c.b1; p.w2f = c.w2f; p.b2 = c.b2; p.gamma = c.gamma; p.eps = c.eps; p.M = c.M;
     p.slab = c.slab; p.counters = c.counters; p.ts = (unsigned long long*)c.ts;
+    p.out_map = c.out_map; p.out_ln_w = c.out_ln_w; p.out_ln_b = c.out_ln_b; p.out_eps = c.out_eps;
     p.ablate = diag_knob("wm_ablate");
     return p;
 }
@@ -585,6 +666,11 @@ inline WinMlpParams make_winmlp_params(const MlpFusedCall& c) {
 size_t winmlp_split_slab_bytes(int64_t M, int C, int nsplit) { return (size_t)((M + 63) / 64) * (size_t)nsplit * 64 * C * 4; }
 
 bool winmlp_supported(int C, int hidden) { return (C == 512 && hidden == 2048) || (C == 256 && hidden == 1024); }
+
+// The stage-exit epilogue lives in the 4-wave C = 256 form (fvit_tune "win_mlp256" = 2, the default) and needs the residual in registers: no layer scale
+bool winmlp_exit_supported(const MlpFusedCall& c) {
+    return c.C == 256 && c.hidden == 1024 && !c.gamma && !c.ts && (c.terms == 1 || c.terms == 2) && tune_get("win_mlp256", 2) == 2;
+}
 
 int launch_winmlp(const MlpFusedCall& c, hipStream_t stream) {
     if (!winmlp_supported(c.C, c.hidden) || c.M <= 0 || !c.x || !c.w1f || !c.w2f) {
@@ -597,7 +683,12 @@ int launch_winmlp(const MlpFusedCall& c, hipStream_t stream) {
     // instantiated: git history, commit "split-hidden form of the C = 512 MLP kernel")
     const int nsplit = (c.C == 512 && c.slab && c.counters && c.nsplit == 2) ? 2 : 1;
     const double flops = 4.0 * c.M * (double)c.C * c.hidden;
-    const double bytes = 8.0 * c.M * (double)c.C + 4.0 * c.C * (double)c.hidden;
+    const bool exit_map = c.out_map.data != nullptr;
+    if (exit_map && !(winmlp_exit_supported(c) && c.out_ln_w && c.out_ln_b)) {
+        set_error("win_mlp: the stage-exit epilogue needs the 4-wave C = 256 form, no layer scale and both LayerNorm2d parameters (C=%d)", c.C);
+        return FVIT_EINVAL;
+    }
+    const double bytes = (exit_map ? 6.0 : 8.0) * c.M * (double)c.C + 4.0 * c.C * (double)c.hidden;   // stage exit: a 16-bit map is written in place of the fp32 rows
     ProfScope prof(FVIT_K_MLP_FUSED, flops, bytes, stream);
     // C = 256 (stage 2): 4 waves x 64 rows, 68 KiB of LDS, two workgroups per CU.  (r02 / r03 also measured 8 waves x 128 rows -- no gain -- and 8 waves x 80 / 96 rows:
     // the launch 24 % shorter, 50.4 -> 38.2 us, and the STEP 1.5 % slower, 124 KiB of LDS and 8 x 200 registers take the whole CU from the other stream shard's kernels;
@@ -648,7 +739,12 @@ int launch_winmlp(const MlpFusedCall& c, hipStream_t stream) {
         else hipLaunchKernelGGL((winmlp_kernel<_Float16, 256, 1024, 4, 2, 4, 1, 1, true>), dim3(grid), dim3(256), 0, stream, p);
     } else
 #endif
-    if (c.C == 512 && nsplit == 2) FVIT_WINMLP_ST(2);
+    if (exit_map) {
+#define FVIT_WINMLP_X(T, SP_) hipLaunchKernelGGL((winmlp_kernel<T, 256, 1024, 4, 2, 4, SP_, 1, false, false, true>), dim3(grid), dim3(256), 0, stream, p)
+        if (c.dtype == FVIT_F16) { if (c.terms == 2) FVIT_WINMLP_X(_Float16, 2); else FVIT_WINMLP_X(_Float16, 1); }
+        else { if (c.terms == 2) FVIT_WINMLP_X(__bf16, 2); else FVIT_WINMLP_X(__bf16, 1); }
+#undef FVIT_WINMLP_X
+    } else if (c.C == 512 && nsplit == 2) FVIT_WINMLP_ST(2);
     // (a 4-deep ring for C = 512 needs 105 spilled registers at 8 waves x 256: not instantiated)
     else if (c.C == 512 && pipe) FVIT_WINMLP_PT(512, 2048, 4, 8);
     else if (c.C == 512) FVIT_WINMLP_T(512, 2048, 4, 8);

@@ -680,6 +680,12 @@ int fvit_sgd_momentum(float* param, float* momentum, const float* grad, int64_t 
  *   r05: "gemm_x3_dual" 1/0 (dual K tiles of the x3 GEMMs vs the K-concatenated walk), "conv_n128_ragged" 1/0 (128 x 128 conv tiles with a ragged last N tile
  *   for Cout % 128 == 64 vs 128 x 64 tiles), "gemm_splitk" 0/1;
  *   r06: "win_mlp_pipe" 1/0 (software-pipelined super-chunk loop of the C = 512 MLP kernel vs the plain loop; bitwise the same result).
+ *   Stage boundaries of fvit_hat_stage_forward(_tail), both default 1, on unpadded levels without propagation and layer scale:
+ *   "stage_entry_fused" 1/0: block 0's fused window attention kernel reads the level's 16-bit channels-last map (8-byte aligned pixels) itself and the fused
+ *   carrier kernel reads ct_init, in place of the window_partition pass and the carrier copy (bitwise the same result; ln1_src entries >= 0 must then name
+ *   local rows, as the tables of every caller here do);
+ *   "stage_exit_fused" 1/0: with a LayerNorm2d tail the last 4-wave C = 256 MLP kernel writes the normalised 16-bit map in place of the window_reverse +
+ *   LayerNorm2d pass (same rounded values, another summation order of the statistics).
  *   Removed in r06 with the kernel instances they selected (all measured no better than the defaults): "gemm_ring", "gemm_3stage_max_grid", "mlp_ring4_max_grid",
  *   "win_mlp256_depth", "win_stage3", "win_mlp256" = 1 / 3, "mlp_variant" = 2 / 4 / 5 / 6.
  * Guarded by a mutex; launches read the values at launch time.
