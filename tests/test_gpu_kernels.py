@@ -438,7 +438,7 @@ def test_conv3x3_dense_k(dt, code, B, Ci, Cv, Co, H, W, stride, act, res, terms)
     lib = _lib.lib()
     g = torch.Generator(device="cpu").manual_seed(Ci + Co + H + Cv)
     x = torch.randn(B, Ci, H, W, generator=g)
-    x[:, Cv:] = 1000.0                                    # poison: a classic contraction would see it (its weights there are zero, but 1000 * 0 must not even be formed from a NaN)
+    x[:, Cv:] = float("nan")                              # poison: the weights there are zero, but 0 x NaN is NaN -- the dense kernel must not even form the product
     xz = x.clone(); xz[:, Cv:] = 0
     x, xz = [t.to(dt).cuda().contiguous(memory_format=torch.channels_last) for t in (x, xz)]
     w = torch.zeros(Co, Ci, 3, 3)
