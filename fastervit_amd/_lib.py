@@ -19,6 +19,7 @@ if os.environ.get("FVIT_LIB_PATH"):
 
 FVIT_ABI_VERSION = 10
 FVIT_F32, FVIT_F16, FVIT_BF16 = 0, 1, 2
+FVIT_U8 = 3   # FvitMapView.dtype of a uint8 image: the fvit_*_u8 entry points only
 FVIT_TILE_N, FVIT_TILE_K = 128, 64
 FVIT_MASK_BIAS = -30000.0
 FVIT_MAX_DENSE_SEQ = 208   # longer window sequences use the online-softmax attention kernel with the compact bias table
@@ -42,6 +43,7 @@ EXPORTED_SYMBOLS = (
     "fvit_prof_records", "fvit_prof_kind_name",
     "fvit_hat_stage_forward_tail", "fvit_rows_avgpool", "fvit_conv3x3_c64_ln2d", "fvit_conv3x3_c128_band_ln2d",
     "fvit_conv3x3", "fvit_conv3x3_route", "fvit_conv3x3_route_name",
+    "fvit_stem_conv3x3s2_u8", "fvit_stem_conv3x3s2_px_u8", "fvit_stem_fused_u8", "fvit_image_normalize_u8",
 )
 # only in libfvit_hip_diag.so (the same sources with -DFVIT_DIAG; FVIT_DIAG=1 selects it): diagnosis entry points of include/fvit_hip.h's #ifdef FVIT_DIAG
 # section.  The shipped library exports none of them and compiles the ablation knobs out (tests/test_abi.py).
@@ -251,6 +253,16 @@ def _declare(lib):
     lib.fvit_stem_conv3x3s2.argtypes = [i32, C.POINTER(FvitMapView), vp, vp, vp, i32, i32, i32, vp]
     lib.fvit_stem_fused.restype = C.c_int
     lib.fvit_stem_fused.argtypes = [i32, C.POINTER(FvitMapView), vp, vp, vp, vp, vp, i32, i32, i32, vp]
+    # the uint8-image forms: the float argument list + const float* norm (scale[3], shift[3] in host memory)
+    fp = C.POINTER(C.c_float)
+    lib.fvit_stem_conv3x3s2_px_u8.restype = C.c_int
+    lib.fvit_stem_conv3x3s2_px_u8.argtypes = list(lib.fvit_stem_conv3x3s2_px.argtypes) + [fp]
+    lib.fvit_stem_conv3x3s2_u8.restype = C.c_int
+    lib.fvit_stem_conv3x3s2_u8.argtypes = list(lib.fvit_stem_conv3x3s2.argtypes) + [fp]
+    lib.fvit_stem_fused_u8.restype = C.c_int
+    lib.fvit_stem_fused_u8.argtypes = list(lib.fvit_stem_fused.argtypes) + [fp]
+    lib.fvit_image_normalize_u8.restype = C.c_int
+    lib.fvit_image_normalize_u8.argtypes = [C.POINTER(FvitMapView), vp, i32, i32, i32, i32, i32, fp, vp, vp]
     lib.fvit_head_logits.restype = C.c_int
     lib.fvit_head_logits.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
     lib.fvit_head_softmax_xent.restype = C.c_int

@@ -167,6 +167,10 @@ class DeployPlan:
                 continue  # HAT parameters are tracked by hat_runtime
             sig.append((p.data_ptr(), p._version))
         sig.append(("options", self.precise, self.conv_weight_terms, self.down_weight_terms, self.dense_k))   # what _build depends on besides the parameters
+        try:   # uint8 images (set_input_norm): a change is picked up by the next eager call, like a weight change
+            sig.append(("input_norm", m.input_norm()))
+        except RuntimeError:   # no default for this in_chans and none set: a uint8 image raises at its call
+            sig.append(("input_norm", None))
         return tuple(sig)
 
     def _cp(self, c):
@@ -522,7 +526,12 @@ class DeployPlan:
     def _stem(self, x):
         """PatchEmbed: conv + BN + ReLU twice, from the caller's image to the map level 0 takes."""
         t, st = self.t, self.t["stem"]
-        k27 = t["stem_k"] is not None and x.shape[1] == 3 and x.dtype in hat_runtime._DT   # the reference's 3 -> 64 first conv: the K = 27 kernels
+        u8 = x.dtype == torch.uint8
+        if u8 and not (t["stem_k"] is not None and x.shape[1] == 3):
+            x, u8 = self.model.normalize_input(x), False   # a stem without a uint8 kernel: one normalisation pass, then the float route
+        # a uint8 image on the K = 27 kernels: normalised at their loads with the model's constants, read from host memory at each launch
+        norm = self.model.input_norm_array() if u8 else None
+        k27 = t["stem_k"] is not None and x.shape[1] == 3 and (u8 or x.dtype in hat_runtime._DT)   # the reference's 3 -> 64 first conv: the K = 27 kernels
         if self.precise:
             if not k27:
                 # a stem other than the reference's 3 -> 64 (in_dim / in_chans kwargs): its first conv as an fp32 PyTorch-ROCm conv
@@ -531,9 +540,12 @@ class DeployPlan:
             else:
                 B, _, Hi, Wi = x.shape
                 y = torch.empty((B, 64, (Hi - 1) // 2 + 1, (Wi - 1) // 2 + 1), dtype=self.dtype, device=x.device, memory_format=torch.channels_last)
-                view = hat_runtime._map_view(x)
-                _lib.check(_lib.lib().fvit_stem_conv3x3s2_px(self.code, view, t["stem_k"].data_ptr(), t["stem_k_lo"].data_ptr(), st.bias0.data_ptr(),
-                                                             y.data_ptr(), B, Hi, Wi, _stream(self.dev)), "fvit_stem_conv3x3s2_px")
+                view = hat_runtime._image_view(x)
+                args = (self.code, view, t["stem_k"].data_ptr(), t["stem_k_lo"].data_ptr(), st.bias0.data_ptr(), y.data_ptr(), B, Hi, Wi, _stream(self.dev))
+                if u8:
+                    _lib.check(_lib.lib().fvit_stem_conv3x3s2_px_u8(*args, norm), "fvit_stem_conv3x3s2_px_u8")
+                else:
+                    _lib.check(_lib.lib().fvit_stem_conv3x3s2_px(*args), "fvit_stem_conv3x3s2_px")
             return (*self._conv_px(y, None, st.conv1, st.bias1, 2, 1), None)
         wk1 = st.conv1.wk
         if self.fused_stem and k27 and wk1 is not None and st.conv1.terms == 1 and tuple(wk1.shape) == (64, 3, 3, 64):
@@ -541,17 +553,23 @@ class DeployPlan:
             H1, W1 = (Hi - 1) // 2 + 1, (Wi - 1) // 2 + 1
             y = torch.empty((B, 64, (H1 - 1) // 2 + 1, (W1 - 1) // 2 + 1), dtype=self.dtype, device=x.device,
                             memory_format=torch.channels_last)
-            view = hat_runtime._map_view(x)
-            _lib.check(_lib.lib().fvit_stem_fused(self.code, view, t["stem_k"].data_ptr(), st.bias0.data_ptr(), wk1.data_ptr(),
-                                                  st.bias1.data_ptr(), y.data_ptr(), B, Hi, Wi, _stream(self.dev)), "fvit_stem_fused")
+            view = hat_runtime._image_view(x)
+            args = (self.code, view, t["stem_k"].data_ptr(), st.bias0.data_ptr(), wk1.data_ptr(), st.bias1.data_ptr(), y.data_ptr(), B, Hi, Wi, _stream(self.dev))
+            if u8:
+                _lib.check(_lib.lib().fvit_stem_fused_u8(*args, norm), "fvit_stem_fused_u8")
+            else:
+                _lib.check(_lib.lib().fvit_stem_fused(*args), "fvit_stem_fused")
             return y
         if k27:
             B, _, Hi, Wi = x.shape   # fused stem kernel reads the caller's image in place (any strides, fp32/16-bit)
             y = torch.empty((B, 64, (Hi - 1) // 2 + 1, (Wi - 1) // 2 + 1), dtype=self.dtype, device=x.device,
                             memory_format=torch.channels_last)
-            view = hat_runtime._map_view(x)
-            _lib.check(_lib.lib().fvit_stem_conv3x3s2(self.code, view, t["stem_k"].data_ptr(), st.bias0.data_ptr(), y.data_ptr(),
-                                                      B, Hi, Wi, _stream(self.dev)), "fvit_stem_conv3x3s2")
+            view = hat_runtime._image_view(x)
+            args = (self.code, view, t["stem_k"].data_ptr(), st.bias0.data_ptr(), y.data_ptr(), B, Hi, Wi, _stream(self.dev))
+            if u8:
+                _lib.check(_lib.lib().fvit_stem_conv3x3s2_u8(*args, norm), "fvit_stem_conv3x3s2_u8")
+            else:
+                _lib.check(_lib.lib().fvit_stem_conv3x3s2(*args), "fvit_stem_conv3x3s2")
             return self._conv(y, st.conv1, st.bias1, 2, 1)
         x = x.to(self.dtype).contiguous(memory_format=torch.channels_last)
         return self._conv(self._conv(x, st.conv0, st.bias0, 2, 1), st.conv1, st.bias1, 2, 1)
@@ -816,6 +834,8 @@ class ShardRunner:
         torch.cuda.synchronize()
 
     def set_input(self, x):
+        if (x.dtype == torch.uint8) != (self.inputs[0].dtype == torch.uint8):   # a copy_ would turn bytes into unnormalised floats (or back)
+            raise RuntimeError(f"ShardRunner: built for {self.inputs[0].dtype} images, set_input got {x.dtype}")
         for dst, src in zip(self.inputs, x.chunk(self.n, dim=0)):
             dst.copy_(src, non_blocking=True)
         torch.cuda.synchronize()

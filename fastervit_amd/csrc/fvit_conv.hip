@@ -479,6 +479,7 @@ struct StemParams {
     void* out;           // [B][Ho][Wo][64]
     int B, Hi, Wi, Ho, Wo, M;
     const void* w_lo;    // PX (fvit_stem_conv3x3s2_px): the second weight term, same layout; the image is split hi + lo in registers
+    float nscale[3], nshift[3];   // U8 instances: the image is uint8 and every gathered byte u of channel c becomes fmaf(u, nscale[c], nshift[c])
 };
 
 __device__ __forceinline__ float stem_load(const FvitMapView& v, int64_t off) {
@@ -487,7 +488,10 @@ __device__ __forceinline__ float stem_load(const FvitMapView& v, int64_t off) {
     return (float)((const __bf16*)v.data)[off];
 }
 
-template <typename T, bool PX = false>
+// U8: the caller's image is uint8 (FVIT_U8) and is normalised at the load; a tap outside the image is a NORMALISED zero (the reference pads after
+// normalising), so the mask is applied behind the fmaf.  The k slots are the float kernel's: the MFMA sees the operands the float kernel sees on the
+// normalised fp32 image, and the results are the same bits.
+template <typename T, bool PX = false, bool U8 = false>
 __global__ __launch_bounds__(256) void stem_conv_kernel(StemParams p) {
     typedef typename Op16<T>::v8 v8;
     const int lane = threadIdx.x & 63;
@@ -513,6 +517,7 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(StemParams p) {
     // this lane's 8 taps (k = 8g + e = ky*9 + kx*3 + c): offsets are pixel independent, computed once
     int64_t toff[8];
     int tky[8], tkx[8];
+    float nsc[8], nsh[8];   // U8: the normalisation constants of each tap's channel
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
         const int k = g * 8 + e;
@@ -520,6 +525,10 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(StemParams p) {
         tky[e] = k < 27 ? ky : -100000;  // padded k slots can never be in range
         tkx[e] = kx;
         toff[e] = c * p.in.stride_c + ky * p.in.stride_h + kx * p.in.stride_w;
+        if constexpr (U8) {
+            nsc[e] = c == 0 ? p.nscale[0] : (c == 1 ? p.nscale[1] : p.nscale[2]);
+            nsh[e] = c == 0 ? p.nshift[0] : (c == 1 ? p.nshift[1] : p.nshift[2]);
+        }
     }
     // grid-stride over blocks of 16 output pixels; one wave per block
     for (int blk = blockIdx.x * 4 + (threadIdx.x >> 6); blk < nblk16; blk += gridDim.x * 4) {
@@ -537,7 +546,9 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(StemParams p) {
             const bool inb = y >= 0 && y < p.Hi && x >= 0 && x < p.Wi;
             // always issue the load (clamped to the pixel's own centre tap, which is always inside), then mask
             const int64_t off = inb ? base + toff[e] : base + p.in.stride_h + p.in.stride_w;
-            const float v0 = stem_load(p.in, off);
+            float v0;
+            if constexpr (U8) v0 = __builtin_fmaf((float)((const uint8_t*)p.in.data)[off], nsc[e], nsh[e]);
+            else v0 = stem_load(p.in, off);
             const float v = inb ? v0 : 0.f;
             xf[e] = (T)v;
             if constexpr (PX) xl[e] = (T)(v - (float)xf[e]);
@@ -1169,6 +1180,7 @@ struct StemFusedParams {
     int tiles_x, tiles_y, tiles;
     unsigned long long* ts;   // TS instance only (fvit_debug_stem_timeline): per wave [workgroup][wave][8] accumulated s_memtime ticks:
                               // 0 phase A (gathers + conv1 + LDS writes), 1 barrier after A, 2 phase B, 3 epilogue, 4 barrier before A, 5 tiles, 6 total
+    float nscale[3], nshift[3];   // IN = uint8_t: every gathered byte u of channel c becomes fmaf(u, nscale[c], nshift[c]) (fvit_stem_fused_u8)
 };
 
 constexpr int SF_ROWS = 2 * HALO_TH + 1, SF_COLS = 2 * HALO_TW + 1;         // 17 x 33 conv1 pixels per tile
@@ -1186,9 +1198,17 @@ constexpr int SF_BATCH = 3;                                                  // 
 // The contraction order changes with it: k slot 8g + e = (ky = g, r9 = e) for g < 3, and the ninth value of each row goes to lane group 3 (k slots 24 + ky,
 // three VALU lane swaps); the first-conv weights are re-ordered to match, once per workgroup, into LDS.  Rows above / below the image are out of the
 // buffer's range and read as zero; the left / right border columns are masked (the run then covers the neighbouring row's pixel).
+// IN = uint8_t (fvit_stem_fused_u8): the image is uint8 and is normalised at the load, value = inside ? fmaf(u, nscale[c], nshift[c]) : 0 -- the zero padding
+// is applied AFTER the normalisation, as the reference does, so a tap outside the image is masked explicitly (an out-of-range load's 0 would normalise
+// to nshift[c]).  Both gathers keep the k slots of their float instance: the MFMA operands, and so the result bits, are those of the float kernel on the
+// normalised fp32 image in the same layout.  The general gather is one byte load per element.  NHWC3 (the decoder's HWC: stride_c 1, stride_w 3): the
+// nine (kx, c) values of a kernel row are nine contiguous BYTES at any alignment (pixel and W * 3 mod 4 decide it): three aligned dword loads from a
+// buffer whose base is the image base rounded down to a dword and whose size is rounded up to one (a dword with a byte of the image in it lies in that
+// byte's page), v_alignbyte_b32 by the offset's low two bits, then v_cvt_f32_ubyte0..3 + v_fma per value.
 template <typename T, typename IN = float, bool TS = false, bool NHWC3 = false>
 __global__ __launch_bounds__(256, 2) void stem_fused_kernel(StemFusedParams p) {
-    static_assert(!NHWC3 || sizeof(IN) == 4, "the contiguous-run gather needs dword-aligned runs: fp32 input");
+    constexpr bool U8IN = sizeof(IN) == 1;
+    static_assert(!NHWC3 || sizeof(IN) == 4 || U8IN, "the contiguous-run gather reads dword-aligned runs (fp32) or aligns byte runs itself (uint8)");
     unsigned long long tsA = 0, tsBar = 0, tsB = 0, tsE = 0, tsBar0 = 0, tsN = 0, tsT0 = 0, tsMark = 0;
     unsigned pf_sink = 0;   // keeps the next-tile touch loads alive
     if constexpr (TS) { tsT0 = __builtin_amdgcn_s_memtime(); }
@@ -1262,12 +1282,17 @@ __global__ __launch_bounds__(256, 2) void stem_fused_kernel(StemFusedParams p) {
 #pragma unroll
             for (int ni = 0; ni < 4; ++ni) w1f[ni] = *(const v8*)(w1s + ((lane_s >> 2) * 16 + ni * 4 + (lane_s & 3)) * 32 + lane_g * 8);
             // one buffer per image: every offset outside [0, Hi Wi 12) -- the rows above and below the image, negative offsets included -- reads as zero
-            const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)p.in.data + (int64_t)b * p.in.stride_b * 4), 0,
-                                                                                   p.Hi * p.Wi * 12, 0x00020000);
+            // uint8: base rounded down to a dword (al = the bytes in front of the image), size rounded up to one; every row is masked explicitly below
+            const uintptr_t ibase = (uintptr_t)p.in.data + (int64_t)b * p.in.stride_b * (int64_t)sizeof(IN);
+            const int al = U8IN ? (int)(ibase & 3) : 0;
+            const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(ibase - al), 0,
+                                                                                   U8IN ? ((al + p.Hi * p.Wi * 3 + 3) & ~3) : p.Hi * p.Wi * 12, 0x00020000);
             const int gy = lane_g < 3 ? lane_g : 2;          // lane group 3 repeats group 2's loads; its own values arrive by lane swaps
             for (int g3 = wave; g3 < SF_GROUPS; g3 += 4 * SF_BATCH) {
                 f4 la[SF_BATCH], lb[SF_BATCH];
                 float lc8[SF_BATCH];
+                unsigned d0[SF_BATCH], d1[SF_BATCH], d2[SF_BATCH], bsh[SF_BATCH];   // uint8: the three dwords around the run and its byte shift
+                bool rowin[SF_BATCH];                                               // uint8: the run's row is inside the image
                 int qv[SF_BATCH], lrv[SF_BATCH], lcv[SF_BATCH];
                 bool v1v[SF_BATCH], lft[SF_BATCH], rgt[SF_BATCH];
 #pragma unroll
@@ -1283,16 +1308,37 @@ __global__ __launch_bounds__(256, 2) void stem_fused_kernel(StemFusedParams p) {
                     // a pixel outside the conv1 map (v1 false) is stored as zero below whatever it read: point it at the image's first run.  At the left / right
                     // border the run starts one pixel later / earlier (and is shifted back in registers below): no access then straddles the start or the end of
                     // the buffer -- a dwordx4 that is PARTLY out of range comes back as zeros altogether (r06: the image's corner pixels were wrong)
-                    const int off = v1 ? ((yi + gy) * p.Wi + xi + (xi < 0 ? 1 : 0) - (xi + 2 >= p.Wi ? 1 : 0)) * 12 : 0;
-                    la[u] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, 0));
-                    lb[u] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, off + 16, 0, 0));
-                    lc8[u] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, off + 32, 0, 0));
+                    const int off = v1 ? ((yi + gy) * p.Wi + xi + (xi < 0 ? 1 : 0) - (xi + 2 >= p.Wi ? 1 : 0)) * (U8IN ? 3 : 12) : 0;
+                    if constexpr (U8IN) {
+                        const int ob = off + al, a0 = ob & ~3;     // a row above the image: a negative (= huge unsigned) offset, out of range, reads 0
+                        rowin[u] = yi + gy >= 0 && yi + gy < p.Hi;
+                        bsh[u] = (unsigned)ob & 3u;
+                        d0[u] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, a0, 0, 0);
+                        d1[u] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, a0 + 4, 0, 0);
+                        d2[u] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, a0 + 8, 0, 0);
+                    } else {
+                        la[u] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, 0));
+                        lb[u] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, off + 16, 0, 0));
+                        lc8[u] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rsrc, off + 32, 0, 0));
+                    }
                 }
 #pragma unroll
                 for (int u = 0; u < SF_BATCH; ++u) {
                     const int q = qv[u], lr = lrv[u], lc = lcv[u];
                     const bool v1 = v1v[u];
-                    const float l9[9] = {la[u][0], la[u][1], la[u][2], la[u][3], lb[u][0], lb[u][1], lb[u][2], lb[u][3], lc8[u]};
+                    float l9[9];
+                    if constexpr (U8IN) {
+                        const unsigned w3[3] = {__builtin_amdgcn_alignbyte(d1[u], d0[u], bsh[u]), __builtin_amdgcn_alignbyte(d2[u], d1[u], bsh[u]),
+                                                __builtin_amdgcn_alignbyte(d2[u], d2[u], bsh[u])};
+#pragma unroll
+                        for (int e = 0; e < 9; ++e) {
+                            const float nv = __builtin_fmaf((float)((w3[e >> 2] >> (8 * (e & 3))) & 0xffu), p.nscale[e % 3], p.nshift[e % 3]);
+                            l9[e] = rowin[u] ? nv : 0.f;   // a row above / below the image: the padding's zero, not nshift
+                        }
+                    } else {
+                        l9[0] = la[u][0]; l9[1] = la[u][1]; l9[2] = la[u][2]; l9[3] = la[u][3];
+                        l9[4] = lb[u][0]; l9[5] = lb[u][1]; l9[6] = lb[u][2]; l9[7] = lb[u][3]; l9[8] = lc8[u];
+                    }
                     float e9[9];
 #pragma unroll
                     for (int e = 0; e < 9; ++e) {
@@ -1350,12 +1396,19 @@ __global__ __launch_bounds__(256, 2) void stem_fused_kernel(StemFusedParams p) {
             // cases it can hit are too -- the per-element k / 9, r9 / 3, four compares and the select chain (~35 VALU per element, 78 % of
             // the kernel in phase A: profiles/r03_stem_phase_accounting.log) collapse to one add and one bit test
             int koff[8];
+            float nsc3[3], nsh3[3];   // uint8: this lane's normalisation constants
             unsigned m_valid = 0, m_ky0 = 0, m_ky2 = 0, m_kx0 = 0, m_kx2 = 0;
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const int k = lane_g * 8 + e;
                 const int ky = k / 9, r9 = k - ky * 9, kx = r9 / 3, c = r9 - kx * 3;
                 koff[e] = c * sc + ky * sh + kx * sw;
+                if constexpr (U8IN) {
+                    if (e < 3) {   // k slot 8g + e holds channel (2g + e) % 3: three constants per lane, slot e takes number e % 3
+                        nsc3[e] = c == 0 ? p.nscale[0] : (c == 1 ? p.nscale[1] : p.nscale[2]);
+                        nsh3[e] = c == 0 ? p.nshift[0] : (c == 1 ? p.nshift[1] : p.nshift[2]);
+                    }
+                }
                 m_valid |= (k < 27 ? 1u : 0u) << e;
                 m_ky0 |= (ky == 0 ? 1u : 0u) << e;
                 m_ky2 |= (ky == 2 ? 1u : 0u) << e;
@@ -1408,7 +1461,8 @@ __global__ __launch_bounds__(256, 2) void stem_fused_kernel(StemFusedParams p) {
                         const bool inb = (mask >> e) & 1u;
                         // always a legal address (the image's first element when masked), then select
                         const unsigned off = inb ? (unsigned)(base + koff[e]) : 0u;
-                        const float val = (float)*(const IN*)(ib + off);
+                        float val = (float)*(const IN*)(ib + off);
+                        if constexpr (U8IN) val = __builtin_fmaf(val, nsc3[e % 3], nsh3[e % 3]);
                         xfb[u][e] = (T)(inb ? val : 0.f);
                     }
                 }
@@ -1840,21 +1894,58 @@ extern "C" int fvit_debug_conv_band_timeline(const void* in, const void* w_frag,
 }
 #endif  // FVIT_DIAG
 
-extern "C" int fvit_stem_conv3x3s2_px(int32_t dtype, const FvitMapView* in, const void* weight, const void* weight_lo, const float* bias, void* out,
-                                      int32_t B, int32_t Hi, int32_t Wi, fvit_stream_t stream);
+// A uint8 image goes through the _u8 entry points only (they carry the normalisation constants) and nothing else does: neither side ever reads
+// the caller's bytes as another element type.  norm: scale[3] then shift[3] in HOST memory, copied into the kernel parameters at launch (no device
+// allocation, no copy: safe under graph capture).
+static bool stem_image_type_ok(const char* entry, const FvitMapView* in, const float* norm, bool u8_entry) {
+    if (!u8_entry && in->dtype == FVIT_U8) {
+        set_error("%s: a uint8 (FVIT_U8) image needs its normalisation constants: call %s_u8", entry, entry);
+        return false;
+    }
+    if (u8_entry && in->dtype != FVIT_U8) {
+        set_error("%s_u8: image dtype %d is not FVIT_U8: call %s", entry, in->dtype, entry);
+        return false;
+    }
+    if (u8_entry && !norm) {
+        set_error("%s_u8: null normalisation constants", entry);
+        return false;
+    }
+    return true;
+}
+
+static int stem_conv_impl(const char* entry, int32_t dtype, const FvitMapView* in, const void* weight, const void* weight_lo, const float* bias, void* out,
+                          int32_t B, int32_t Hi, int32_t Wi, fvit_stream_t stream, const float* norm, bool u8_entry);
 
 extern "C" int fvit_stem_conv3x3s2(int32_t dtype, const FvitMapView* in, const void* weight, const float* bias, void* out, int32_t B,
                                    int32_t Hi, int32_t Wi, fvit_stream_t stream) {
-    return fvit_stem_conv3x3s2_px(dtype, in, weight, nullptr, bias, out, B, Hi, Wi, stream);
+    return stem_conv_impl("fvit_stem_conv3x3s2", dtype, in, weight, nullptr, bias, out, B, Hi, Wi, stream, nullptr, false);
 }
 
 extern "C" int fvit_stem_conv3x3s2_px(int32_t dtype, const FvitMapView* in, const void* weight, const void* weight_lo, const float* bias, void* out,
                                       int32_t B, int32_t Hi, int32_t Wi, fvit_stream_t stream) {
+    return stem_conv_impl("fvit_stem_conv3x3s2_px", dtype, in, weight, weight_lo, bias, out, B, Hi, Wi, stream, nullptr, false);
+}
+
+extern "C" int fvit_stem_conv3x3s2_u8(int32_t dtype, const FvitMapView* in, const void* weight, const float* bias, void* out, int32_t B,
+                                      int32_t Hi, int32_t Wi, fvit_stream_t stream, const float* norm) {
+    return stem_conv_impl("fvit_stem_conv3x3s2", dtype, in, weight, nullptr, bias, out, B, Hi, Wi, stream, norm, true);
+}
+
+extern "C" int fvit_stem_conv3x3s2_px_u8(int32_t dtype, const FvitMapView* in, const void* weight, const void* weight_lo, const float* bias, void* out,
+                                         int32_t B, int32_t Hi, int32_t Wi, fvit_stream_t stream, const float* norm) {
+    return stem_conv_impl("fvit_stem_conv3x3s2_px", dtype, in, weight, weight_lo, bias, out, B, Hi, Wi, stream, norm, true);
+}
+
+static int stem_conv_impl(const char* entry, int32_t dtype, const FvitMapView* in, const void* weight, const void* weight_lo, const float* bias, void* out,
+                          int32_t B, int32_t Hi, int32_t Wi, fvit_stream_t stream, const float* norm, bool u8_entry) {
     if (!in || !in->data || !weight || !bias || !out || B <= 0 || Hi <= 0 || Wi <= 0) {
         set_error("stem_conv: null or empty argument");
         return FVIT_EINVAL;
     }
+    if (!stem_image_type_ok(entry, in, norm, u8_entry)) return FVIT_EINVAL;
+    const bool u8 = u8_entry;
     StemParams p;
+    for (int c = 0; c < 3; ++c) { p.nscale[c] = u8 ? norm[c] : 1.f; p.nshift[c] = u8 ? norm[3 + c] : 0.f; }
     p.in = *in; p.w = weight; p.w_lo = weight_lo; p.bias = bias; p.out = out; p.B = B; p.Hi = Hi; p.Wi = Wi;
     p.Ho = (Hi - 1) / 2 + 1;
     p.Wo = (Wi - 1) / 2 + 1;
@@ -1867,9 +1958,13 @@ extern "C" int fvit_stem_conv3x3s2_px(int32_t dtype, const FvitMapView* in, cons
     const int nblk16 = (p.M + 15) / 16;
     int grid = (nblk16 + 3) / 4;
     if (grid > 256 * 32) grid = 256 * 32;
-    const double bytes = (double)B * 3 * Hi * Wi * (in->dtype == FVIT_F32 ? 4 : 2) + 2.0 * M * 64;
+    const double bytes = (double)B * 3 * Hi * Wi * (u8 ? 1 : in->dtype == FVIT_F32 ? 4 : 2) + 2.0 * M * 64;
     ProfScope prof(FVIT_K_CONV, 2.0 * M * 64 * 27, bytes, (hipStream_t)stream);
-    if (dtype == FVIT_F16 && weight_lo) hipLaunchKernelGGL((stem_conv_kernel<_Float16, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
+    if (u8 && dtype == FVIT_F16 && weight_lo) hipLaunchKernelGGL((stem_conv_kernel<_Float16, true, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
+    else if (u8 && dtype == FVIT_BF16 && weight_lo) hipLaunchKernelGGL((stem_conv_kernel<__bf16, true, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
+    else if (u8 && dtype == FVIT_F16) hipLaunchKernelGGL((stem_conv_kernel<_Float16, false, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
+    else if (u8 && dtype == FVIT_BF16) hipLaunchKernelGGL((stem_conv_kernel<__bf16, false, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
+    else if (dtype == FVIT_F16 && weight_lo) hipLaunchKernelGGL((stem_conv_kernel<_Float16, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
     else if (dtype == FVIT_BF16 && weight_lo) hipLaunchKernelGGL((stem_conv_kernel<__bf16, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
     else if (dtype == FVIT_F16) hipLaunchKernelGGL((stem_conv_kernel<_Float16>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
     else if (dtype == FVIT_BF16) hipLaunchKernelGGL((stem_conv_kernel<__bf16>), dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
@@ -1881,11 +1976,16 @@ extern "C" int fvit_stem_conv3x3s2_px(int32_t dtype, const FvitMapView* in, cons
 }
 
 static int stem_fused_impl(int32_t dtype, const FvitMapView* in, const void* w1, const float* b1, const void* w2, const float* b2,
-                           void* out, int32_t B, int32_t Hi, int32_t Wi, fvit_stream_t stream, void* stamps);
+                           void* out, int32_t B, int32_t Hi, int32_t Wi, fvit_stream_t stream, void* stamps, const float* norm = nullptr, bool u8_entry = false);
 
 extern "C" int fvit_stem_fused(int32_t dtype, const FvitMapView* in, const void* w1, const float* b1, const void* w2, const float* b2,
                                void* out, int32_t B, int32_t Hi, int32_t Wi, fvit_stream_t stream) {
     return stem_fused_impl(dtype, in, w1, b1, w2, b2, out, B, Hi, Wi, stream, nullptr);
+}
+
+extern "C" int fvit_stem_fused_u8(int32_t dtype, const FvitMapView* in, const void* w1, const float* b1, const void* w2, const float* b2,
+                                  void* out, int32_t B, int32_t Hi, int32_t Wi, fvit_stream_t stream, const float* norm) {
+    return stem_fused_impl(dtype, in, w1, b1, w2, b2, out, B, Hi, Wi, stream, nullptr, norm, true);
 }
 
 // diagnosis: the fp16 kernel with per-wave phase accumulators (u64 [workgroups <= 512][4 waves][8]: ticks in phase A, barrier after A, phase B,
@@ -1899,11 +1999,13 @@ extern "C" int fvit_debug_stem_timeline(const FvitMapView* in, const void* w1, c
 #endif  // FVIT_DIAG
 
 static int stem_fused_impl(int32_t dtype, const FvitMapView* in, const void* w1, const float* b1, const void* w2, const float* b2,
-                           void* out, int32_t B, int32_t Hi, int32_t Wi, fvit_stream_t stream, void* stamps) {
+                           void* out, int32_t B, int32_t Hi, int32_t Wi, fvit_stream_t stream, void* stamps, const float* norm, bool u8_entry) {
     if (!in || !in->data || !w1 || !b1 || !w2 || !b2 || !out || B <= 0 || Hi <= 0 || Wi <= 0) {
         set_error("stem_fused: null or empty argument");
         return FVIT_EINVAL;
     }
+    if (!stem_image_type_ok("fvit_stem_fused", in, norm, u8_entry)) return FVIT_EINVAL;
+    const bool u8 = u8_entry;
     if (fvit::ablate_skip(128)) return FVIT_OK;
     StemFusedParams p;
     p.in = *in; p.w1 = w1; p.b1 = b1; p.w2 = w2; p.b2 = b2; p.out = out; p.B = B; p.Hi = Hi; p.Wi = Wi;
@@ -1918,15 +2020,22 @@ static int stem_fused_impl(int32_t dtype, const FvitMapView* in, const void* w1,
     }
     p.tiles = (int)tiles;
     p.ts = (unsigned long long*)stamps;
+    for (int c = 0; c < 3; ++c) { p.nscale[c] = u8 ? norm[c] : 1.f; p.nshift[c] = u8 ? norm[3 + c] : 0.f; }
     int maxgrid = tune_get("stem_fused_grid", 512);
     if (maxgrid < 8) maxgrid = 8;
     const int grid = p.tiles < maxgrid ? p.tiles : maxgrid;
     // fp32 channels-last image (stride_c 1, stride_w 3, rows and images dword-addressable from the image base with 32-bit offsets): the contiguous-run gather
-    const bool nhwc3 = in->dtype == FVIT_F32 && in->stride_c == 1 && in->stride_w == 3 && in->stride_h == 3 * (int64_t)Wi && (int64_t)Hi * Wi * 12 < 0x7fffff00 &&
-                       tune_get("stem_nhwc3", 1);
+    // uint8 channels-last (the decoder's HWC): the same gather on nine contiguous bytes (at least two columns: a run never spans more than the row's neighbours)
+    const bool nhwc3 = (in->dtype == FVIT_F32 || (u8 && Wi >= 2)) && in->stride_c == 1 && in->stride_w == 3 && in->stride_h == 3 * (int64_t)Wi &&
+                       (int64_t)Hi * Wi * 12 < 0x7fffff00 && tune_get("stem_nhwc3", 1);
+    if (u8 && !nhwc3 && ((in->stride_c < 0 ? -in->stride_c : in->stride_c) * 2 + (in->stride_h < 0 ? -in->stride_h : in->stride_h) * (int64_t)(Hi + 2) +
+                         (in->stride_w < 0 ? -in->stride_w : in->stride_w) * (int64_t)(Wi + 2)) > 0x7fffff00) {
+        set_error("stem_fused_u8: one image of the view spans more than 2 GiB");
+        return FVIT_EINVAL;
+    }
     const size_t lds = 1024 + SF_LDS + (nhwc3 ? 4096 : 0);
     const double M1 = (double)B * p.H1 * p.W1, M2 = (double)B * p.H2 * p.W2;
-    const double bytes = (double)B * 3 * Hi * Wi * (in->dtype == FVIT_F32 ? 4 : 2) + 2.0 * M2 * 64;
+    const double bytes = (double)B * 3 * Hi * Wi * (u8 ? 1 : in->dtype == FVIT_F32 ? 4 : 2) + 2.0 * M2 * 64;
     ProfScope prof(FVIT_K_CONV, 2.0 * M1 * 64 * 27 + 2.0 * M2 * 64 * 576, bytes, (hipStream_t)stream);
     prof_note("stem_fused_kernel", grid);
 #define FVIT_STEM_LAUNCH(T_, IN_, TS_)                                                                                                   \
@@ -1945,7 +2054,9 @@ static int stem_fused_impl(int32_t dtype, const FvitMapView* in, const void* w1,
     } while (0)
 #define FVIT_STEM_IN(T_)                                                                   \
     do {                                                                                   \
-        if (nhwc3) FVIT_STEM_LAUNCH4(T_, float, false, true);                               \
+        if (nhwc3 && u8) FVIT_STEM_LAUNCH4(T_, uint8_t, false, true);                       \
+        else if (u8) FVIT_STEM_LAUNCH(T_, uint8_t, false);                                  \
+        else if (nhwc3) FVIT_STEM_LAUNCH4(T_, float, false, true);                          \
         else if (in->dtype == FVIT_F32) FVIT_STEM_LAUNCH(T_, float, false);                \
         else if (in->dtype == FVIT_F16) FVIT_STEM_LAUNCH(T_, _Float16, false);             \
         else if (in->dtype == FVIT_BF16) FVIT_STEM_LAUNCH(T_, __bf16, false);              \

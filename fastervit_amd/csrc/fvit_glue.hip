@@ -252,12 +252,88 @@ int map_pad_launch(const T* in, T* out, int B, int H, int W, int Hp, int Wp, int
     return check_launch("map_pad");
 }
 
+// uint8 image -> normalised fp32 image (fvit_image_normalize_u8): out = masked ? 0 : fmaf(u, scale[c], shift[c]), the formula of the uint8 stem kernels,
+// for every caller the fused stems do not cover.  The input is any strided (B, C, H, W) uint8 view, the output a dense fp32 tensor, planar (CL = false:
+// [B][C][H][W]) or channels-last (CL = true: [B][H][W][C]).  One thread owns the four output elements of one 16-byte-aligned quad (one 16-byte store;
+// ``lead`` = the elements between the quad boundary in front of out and out itself; the first and last quad of a range that does not start or end
+// on one store element by element): one 64-bit division finds its image, the position inside the image is 32-bit arithmetic and advances like an
+// odometer.  HBM-bound: 1 byte read and 4 written per element.
+constexpr int NORM_MAXC = 16;
+struct ImageNormParams {
+    FvitMapView in;
+    float* out;
+    const uint8_t* mask;   // [B][H][W] bool (non-zero = padded pixel -> 0) or null
+    int64_t total;         // B * C * H * W
+    int per_image;         // C * H * W < 2^31
+    int C, H, W, lead;
+    float scale[NORM_MAXC], shift[NORM_MAXC];
+};
+
+template <bool CL>
+__global__ __launch_bounds__(256) void image_normalize_u8_kernel(ImageNormParams p) {
+    __shared__ float sc[NORM_MAXC], sf[NORM_MAXC];
+    if (threadIdx.x < NORM_MAXC) { sc[threadIdx.x] = p.scale[threadIdx.x]; sf[threadIdx.x] = p.shift[threadIdx.x]; }
+    __syncthreads();
+    const int64_t i0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4 - p.lead;   // out + i0 is 16-byte aligned
+    if (i0 >= p.total) return;
+    const int64_t first = i0 < 0 ? 0 : i0;
+    int64_t b = first / p.per_image;
+    const int r = (int)(first - b * p.per_image);
+    int c, y, x;
+    if (CL) { const int pix = r / p.C; c = r - pix * p.C; y = pix / p.W; x = pix - y * p.W; }
+    else { const int hw = p.H * p.W; c = r / hw; const int rem = r - c * hw; y = rem / p.W; x = rem - y * p.W; }
+    const uint8_t* __restrict__ src = (const uint8_t*)p.in.data;
+    float v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const bool ok = i0 + j >= 0 && i0 + j < p.total;
+        v[j] = 0.f;
+        if (!ok) continue;
+        const uint8_t u = src[b * p.in.stride_b + c * p.in.stride_c + y * p.in.stride_h + x * p.in.stride_w];
+        v[j] = (p.mask && p.mask[(b * p.H + y) * p.W + x]) ? 0.f : __builtin_fmaf((float)u, sc[c], sf[c]);
+        // the next output element: channels-last runs c, x, y, b; planar x, y, c, b
+        if (CL) { if (++c == p.C) { c = 0; if (++x == p.W) { x = 0; if (++y == p.H) { y = 0; ++b; } } } }
+        else { if (++x == p.W) { x = 0; if (++y == p.H) { y = 0; if (++c == p.C) { c = 0; ++b; } } } }
+    }
+    if (i0 >= 0 && i0 + 4 <= p.total) *(f4*)(p.out + i0) = (f4){v[0], v[1], v[2], v[3]};
+    else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (i0 + j >= 0 && i0 + j < p.total) p.out[i0 + j] = v[j];
+    }
+}
+
 }  // namespace
 }  // namespace fvit
 
 using namespace fvit;
 
 extern "C" {
+
+int fvit_image_normalize_u8(const FvitMapView* in, float* out, int32_t channels_last, int32_t B, int32_t C, int32_t H, int32_t W, const float* norm,
+                            const void* mask, fvit_stream_t stream) {
+    if (!in || !in->data || !out || !norm || B <= 0 || C <= 0 || C > NORM_MAXC || H <= 0 || W <= 0 || (int64_t)C * H * W > INT32_MAX ||
+        ((uintptr_t)out & 3)) {
+        set_error("image_normalize_u8: bad arguments (in_chans=%d in 1..%d, one image below 2^31 elements, out 4-byte aligned)", C, NORM_MAXC);
+        return FVIT_EINVAL;
+    }
+    if (in->dtype != FVIT_U8) {
+        set_error("image_normalize_u8: image dtype %d is not FVIT_U8", in->dtype);
+        return FVIT_EINVAL;
+    }
+    ImageNormParams p;
+    p.in = *in; p.out = out; p.mask = (const uint8_t*)mask; p.C = C; p.H = H; p.W = W;
+    p.per_image = C * H * W;
+    p.total = (int64_t)B * p.per_image;
+    p.lead = (int)(((uintptr_t)out & 15) >> 2);
+    for (int c = 0; c < NORM_MAXC; ++c) { p.scale[c] = c < C ? norm[c] : 0.f; p.shift[c] = c < C ? norm[C + c] : 0.f; }
+    const int64_t blocks = (p.total + p.lead + 1023) / 1024;
+    if (blocks > INT32_MAX) { set_error("image_normalize_u8: too many elements"); return FVIT_EINVAL; }
+    ProfScope prof(FVIT_K_OTHER, 0.0, 5.0 * p.total, (hipStream_t)stream);
+    if (channels_last) hipLaunchKernelGGL((image_normalize_u8_kernel<true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL((image_normalize_u8_kernel<false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
+    return check_launch("image_normalize_u8");
+}
 
 int fvit_bias_act_cl(int32_t dtype, void* x, const float* bias, int64_t n_pixels, int32_t C, int32_t act, fvit_stream_t stream) {
     if (!x || !bias || n_pixels <= 0 || C <= 0 || (C % 4) || act < 0 || act > 2) {

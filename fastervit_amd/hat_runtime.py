@@ -80,6 +80,109 @@ def _map_view(t: torch.Tensor) -> FvitMapView:
 
 
 # --------------------------------------------------------------------------------------------
+# uint8 images.  ``model(u8) == model(normalise(u8))`` with normalise(u)[c] = fmaf(u, scale[c], shift[c]) in fp32,
+# scale = fp32(1 / (255 std)), shift = fp32(-mean / std): the uint8 stem kernels apply it at the load, ``normalize_u8`` is the same formula as a
+# pass of its own for every route without such a kernel.  A uint8 map is an IMAGE: ``_image_view`` is for the stem / normalise entry points only,
+# ``_DT`` / ``_map_view`` keep refusing it, so no uint8 map reaches a HAT stage.
+IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+
+
+def _image_view(t: torch.Tensor) -> FvitMapView:
+    if t.dtype == torch.uint8:
+        sb, sc, sh, sw = t.stride()
+        return FvitMapView(t.data_ptr(), sb, sc, sh, sw, _lib.FVIT_U8, 0)
+    return _map_view(t)
+
+
+def input_norm_constants(mean, std, in_chans: int):
+    """``(scale, shift)`` as tuples of fp32 values (held as Python floats): computed in fp64 and rounded once."""
+    import numpy as np
+    mean, std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
+    if len(mean) != in_chans or len(std) != in_chans:
+        raise ValueError(f"set_input_norm: mean and std need one value per input channel (in_chans = {in_chans}), got {len(mean)} and {len(std)}")
+    if not all(v > 0.0 and v < float("inf") for v in std) or not all(abs(v) < float("inf") for v in mean):
+        raise ValueError("set_input_norm: every std must be > 0 (and mean / std finite)")
+    scale = tuple(float(np.float32(1.0 / (255.0 * s_))) for s_ in std)
+    shift = tuple(float(np.float32(-m_ / s_)) for m_, s_ in zip(mean, std))
+    return scale, shift
+
+
+class InputNorm:
+    """Mixin of the models: the normalisation a uint8 image gets (``set_input_norm``); float images are taken as they are."""
+
+    def _in_chans(self) -> int:
+        return self.patch_embed.conv_down[0].in_channels
+
+    def set_input_norm(self, mean, std):
+        """Per-channel ``mean`` / ``std`` (in 0..1 units, as timm's ``default_cfg``) of uint8 inputs: ``model(u8) == model((u8 / 255 - mean) / std)`` with
+        the right side evaluated as ``fmaf(u8, scale, shift)`` in fp32.  Eager calls pick a change up at once (a deploy plan like a weight change); a
+        compiled runner keeps the constants of its capture until ``recompile()``.  Returns ``self``."""
+        sc, sf = input_norm_constants(mean, std, self._in_chans())
+        self.__dict__["_input_norm"] = (sc, sf)
+        return self
+
+    def input_norm(self):
+        """``(scale, shift)``, tuples of fp32 values; the default is ``default_cfg``'s mean / std where the model has them, else ImageNet's."""
+        got = self.__dict__.get("_input_norm")
+        cfg = getattr(self, "default_cfg", None) or {}
+        key = (cfg.get("mean"), cfg.get("std")) if isinstance(cfg, dict) else (None, None)
+        key = tuple(None if k is None else tuple(k) for k in key)
+        if got is None or (len(got) == 3 and got[2] != key):
+            n = self._in_chans()
+            mean = key[0] if key[0] is not None and len(key[0]) == n else (IMAGENET_MEAN if n == 3 else None)
+            std = key[1] if key[1] is not None and len(key[1]) == n else (IMAGENET_STD if n == 3 else None)
+            if mean is None or std is None:
+                raise RuntimeError(f"uint8 input: no default normalisation for in_chans = {n}; call set_input_norm(mean, std)")
+            sc, sf = input_norm_constants(mean, std, n)
+            got = self.__dict__["_input_norm"] = (sc, sf, key)   # a default: follows default_cfg
+        return got[:2]
+
+    def input_norm_array(self):
+        """scale + shift as the host float array the ``fvit_*_u8`` entry points read at the call."""
+        sc, sf = self.input_norm()
+        return (C.c_float * (2 * len(sc)))(*sc, *sf)
+
+    def normalize_input(self, x: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """uint8 image -> the fp32 image it stands for (identity for every other dtype)."""
+        if x.dtype != torch.uint8:
+            return x
+        _require_gpu(x, type(self).__name__)
+        return normalize_u8(x, self.input_norm_array(), mask)
+
+
+def normalize_u8(x: torch.Tensor, norm, mask: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fvit_image_normalize_u8: (B, C, H, W) uint8, any strides -> fp32 in the same memory format (channels-last stays channels-last, everything else
+    becomes planar); ``norm``: ctypes float array scale[C] + shift[C]; ``mask``: optional (B, H, W) bool, True pixels become 0; ``out``: a dense
+    fp32 tensor of x's shape to write instead (planar or channels-last: its own format decides)."""
+    if x.dtype != torch.uint8 or x.dim() != 4:
+        raise RuntimeError(f"normalize_u8: expected a (B, C, H, W) uint8 image, got {tuple(x.shape)} {x.dtype}")
+    _require_gpu(x, "normalize_u8")
+    if x.requires_grad:
+        raise RuntimeError("normalize_u8: a uint8 image cannot require grad")
+    B, C_, H, W = x.shape
+    if len(norm) != 2 * C_:
+        raise RuntimeError(f"normalize_u8: {len(norm) // 2} normalisation constants for {C_} channels; call set_input_norm(mean, std)")
+    if out is None:
+        cl = C_ > 1 and x.stride(1) == 1 and x.stride(3) == C_
+        out = torch.empty((B, C_, H, W), dtype=torch.float32, device=x.device, memory_format=torch.channels_last if cl else torch.contiguous_format)
+    else:
+        cl = not out.is_contiguous()
+        if out.dtype != torch.float32 or out.shape != x.shape or out.device != x.device or \
+                not (out.is_contiguous() or out.is_contiguous(memory_format=torch.channels_last)):
+            raise RuntimeError("normalize_u8: out must be a dense fp32 tensor (planar or channels-last) of the image's shape on its device")
+    if out.numel() == 0:
+        return out
+    if mask is not None:
+        if mask.dtype != torch.bool or tuple(mask.shape) != (B, H, W) or mask.device != x.device:
+            raise RuntimeError(f"normalize_u8: mask must be a (B, H, W) bool tensor on the image's device, got {tuple(mask.shape)} {mask.dtype}")
+        mask = mask.contiguous()
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().fvit_image_normalize_u8(_image_view(x), out.data_ptr(), 1 if cl else 0, B, C_, H, W, norm,
+                                                      mask.data_ptr() if mask is not None else None, _stream_ptr(x.device)), "fvit_image_normalize_u8")
+    return out
+
+
+# --------------------------------------------------------------------------------------------
 # index tables
 # --------------------------------------------------------------------------------------------
 def build_tables(sr0: int, sr1: int, ws: int, cw: int, hier: bool):

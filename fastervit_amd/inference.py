@@ -26,6 +26,10 @@ class CompiledInference:
     * ``join_from`` (optional): the stream shards join in front of that level and the rest of the network runs on the whole batch.
     * ``precise`` (optional): the two-term-stream conv plan (``DeployPlan.precise``).
     * a weight update after compilation is NOT picked up by the graph (its packed copies are baked in); call ``recompile()``.
+    * a uint8 ``example`` compiles a uint8 runner: ``static_x`` is uint8 (a quarter of the copy-in) and the graph holds the uint8 stem kernel with the
+      model's normalisation constants baked in (``set_input_norm`` afterwards needs ``recompile()``, like a weight update).  Such a runner takes uint8
+      batches only.  A float runner given a uint8 batch normalises it into its static buffer with ``fvit_image_normalize_u8`` (one pass, current
+      constants) -- never a ``copy_`` that would turn bytes into unnormalised floats.
     """
 
     def __init__(self, model, example: torch.Tensor, dtype=torch.float16, streams: int = 3, graph: bool = True, join_from=None,
@@ -98,10 +102,8 @@ class CompiledInference:
         if tuple(x.shape[1:]) != tuple(self.static_x.shape[1:]) or n > self.max_batch:
             raise RuntimeError(f"{name}: input {tuple(x.shape)} does not fit the compiled shape {tuple(self.static_x.shape)}")
         with torch.no_grad(), torch.cuda.device(self.device):
-            if n == self.max_batch:
-                self.static_x.copy_(x, non_blocking=True)
-            else:
-                self.static_x[:n].copy_(x, non_blocking=True)
+            self._copy_in(x)
+            if n < self.max_batch:
                 self.static_x[n:].zero_()
             if self.graph is not None:
                 self.graph.replay()
@@ -110,6 +112,24 @@ class CompiledInference:
         if isinstance(self.static_y, tuple):   # a plan that returns several maps (the detection backbone)
             return tuple(y[:n] for y in self.static_y)
         return self.static_y[:n]
+
+
+    def _copy_in(self, x: torch.Tensor):
+        """``x`` into the first rows of the static input: a copy of the same kind of image, or the normalisation of a uint8 batch into a float buffer."""
+        sx, n = self.static_x, x.shape[0]
+        dst = sx if n == sx.shape[0] else sx[:n]
+        if (x.dtype == torch.uint8) == (sx.dtype == torch.uint8):
+            dst.copy_(x, non_blocking=True)
+        elif sx.dtype == torch.uint8:
+            raise RuntimeError(f"{type(self).__name__}: the runner was compiled for {sx.dtype} images (normalised inside its stem kernel) but was called with "
+                               f"{x.dtype}; compile a runner with an example of that dtype")
+        else:
+            from . import hat_runtime
+            norm = self.model.input_norm_array()
+            if sx.dtype == torch.float32 and (sx.is_contiguous() or sx.is_contiguous(memory_format=torch.channels_last)):
+                hat_runtime.normalize_u8(x, norm, out=dst)
+            else:
+                dst.copy_(hat_runtime.normalize_u8(x, norm), non_blocking=True)
 
 
 class CompiledBackboneInference(CompiledInference):
@@ -192,7 +212,8 @@ class PipelinedInference:
 
     def set_input(self, x: torch.Tensor):
         for r in self.runners:
-            r.static_x.copy_(x, non_blocking=True)
+            with torch.no_grad(), torch.cuda.device(self.device):
+                r._copy_in(x)
         torch.cuda.synchronize(self.device)
 
     def launch(self):

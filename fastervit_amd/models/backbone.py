@@ -36,6 +36,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ..hat_runtime import InputNorm
 from .faster_vit import FasterViTLayer, HatSwitches, PatchEmbed
 
 # DET:853-960, the builder's eight configurations
@@ -93,10 +94,14 @@ class BackboneLayer(FasterViTLayer):
         return (x if self.downsample is None else self.downsample(x)), x
 
 
-class FasterViTBackbone(HatSwitches, nn.Module):
+class FasterViTBackbone(HatSwitches, InputNorm, nn.Module):
     """DET:710-850.  ``forward(tensor_list)`` takes any object with ``.tensors`` (B, 3, H, W) and ``.mask`` (B, H, W) and returns
     ``{k: type(tensor_list)(feature, mask)}`` for the k-th entry of ``out_indices``; ``forward_features(x)`` returns the tuple of NCHW
-    fp32 maps.  Any H, W: detection batches change size from call to call."""
+    fp32 maps.  Any H, W: detection batches change size from call to call.
+
+    uint8 images (``set_input_norm``) stand for their normalised fp32 image, as for the classifier: ``forward_features(u8)`` of a
+    deployed backbone normalises inside the stem kernel, every other route runs one normalisation pass first; ``forward(tensor_list)`` passes
+    ``tensor_list.mask`` to that pass so that padded pixels are 0, as they are in a float ``NestedTensor`` (DINO pads after normalising)."""
 
     def __init__(self, dim, in_dim, depths, ct_size, mlp_ratio, num_heads, window_size=(7, 7, 7, 7), resolution=224, drop_path_rate=0.2,
                  in_chans=3, num_classes=1000, qkv_bias=True, qk_scale=None, drop_rate=0., attn_drop_rate=0., layer_scale=None,
@@ -167,7 +172,7 @@ class FasterViTBackbone(HatSwitches, nn.Module):
         from ..hat_backward import feature_tap_with_grad
         from ..hat_runtime import _require_gpu
         _require_gpu(x, "FasterViTBackbone")
-        x = self.patch_embed(x)
+        x = self.patch_embed(self.normalize_input(x))
         outs = []
         for idx, level in enumerate(self.levels):
             x, xo = level(x)
@@ -212,6 +217,8 @@ class FasterViTBackbone(HatSwitches, nn.Module):
             return self._forward_features_grad(x)
         self._check_inference(x)
         plan = self.__dict__.get("_deploy_plan")
+        if plan is None or getattr(self, "_is_replica", False):
+            x = self.normalize_input(x)   # module mode has no uint8 stem
         if plan is not None and not getattr(self, "_is_replica", False):
             with torch.no_grad():
                 return plan.forward(x)
@@ -226,7 +233,8 @@ class FasterViTBackbone(HatSwitches, nn.Module):
         return tuple(outs)
 
     def forward(self, tensor_list):
-        return self._nested(self.forward_features(tensor_list.tensors), tensor_list)
+        # uint8 tensors: normalised here, with the mask, so that padded pixels are the float NestedTensor's zeros (not normalise(0))
+        return self._nested(self.forward_features(self.normalize_input(tensor_list.tensors, tensor_list.mask)), tensor_list)
 
     @staticmethod
     def _nested(outs, tensor_list):

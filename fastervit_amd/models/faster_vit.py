@@ -25,6 +25,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ..hat_runtime import InputNorm
 from .registry import register_pip_model
 
 _TIMM_PENDING = []  # entrypoints to (re-)register with timm, see register_with_timm()
@@ -471,8 +472,14 @@ class HatSwitches:
         return self
 
 
-class FasterViT(HatSwitches, nn.Module):
-    """FV:846-972 / AR:873-1002."""
+class FasterViT(HatSwitches, InputNorm, nn.Module):
+    """FV:846-972 / AR:873-1002.
+
+    Inputs: a float image is taken as it is (already normalised).  A uint8 image -- what a decoder produces, (B, C, H, W) in any memory format -- is
+    normalised on the GPU with the constants of ``set_input_norm`` (default: ``default_cfg``'s mean / std, else ImageNet's):
+    ``model(u8) == model(normalise(u8))`` bit for bit, normalise(u)[c] = fmaf(u, scale[c], shift[c]) in fp32.  The deploy plan's 3 -> 64 stem kernels
+    do it at their loads; everywhere else (module mode, train mode, other stems, the autocast plan, DataParallel replicas) one ``fvit_image_normalize_u8``
+    pass runs first.  A uint8 input never requires grad; a CPU tensor raises as a float one does."""
 
     def __init__(self, dim, in_dim, depths, window_size, ct_size, mlp_ratio, num_heads, resolution=224,
                  drop_path_rate=0.2, in_chans=3, num_classes=1000, qkv_bias=True, qk_scale=None, drop_rate=0.,
@@ -547,6 +554,7 @@ class FasterViT(HatSwitches, nn.Module):
                     H, W = (H - 1) // 2 + 1, (W - 1) // 2 + 1
 
     def forward_features(self, x):
+        x = self.normalize_input(x)   # a uint8 image: one normalisation pass (the module path has no uint8 stem)
         self._check_grad_request(x)
         x = self.patch_embed(x)
         for level in self.levels:
@@ -620,8 +628,10 @@ class FasterViT(HatSwitches, nn.Module):
         return self._set_hat_backward(bool(on), bool(on and long_sequences), "model", refused_long=None)
 
     def forward(self, x):
-        self._check_grad_request(x)   # eval on the GPU, forward-only HIP stages: a caller asking for d/dx gets the gradient or an error, not zeros
         plan = self.__dict__.get("_deploy_plan")
+        if x.dtype == torch.uint8 and not (plan is not None and x.is_cuda and not self.training and not getattr(self, "_is_replica", False)):
+            x = self.normalize_input(x)   # every route but the deploy plan (whose stem kernels read the bytes themselves): normalise first
+        self._check_grad_request(x)   # eval on the GPU, forward-only HIP stages: a caller asking for d/dx gets the gradient or an error, not zeros
         # nn.DataParallel replicas share __dict__ with the original: the plan's folded weights live on the original's device, so
         # replicas run the module path (per-device HAT state in hat_runtime)
         if plan is not None and x.is_cuda and not self.training and not getattr(self, "_is_replica", False):

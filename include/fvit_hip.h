@@ -42,6 +42,9 @@ extern "C" {
 #define FVIT_F32 0
 #define FVIT_F16 1
 #define FVIT_BF16 2
+/* FvitMapView.dtype only: a uint8 IMAGE (what a decoder produces).  Accepted by the fvit_*_u8 entry points alone, which normalise it at the load;
+ * every other entry point refuses it (FVIT_EINVAL), and no uint8 map ever reaches a HAT stage. */
+#define FVIT_U8 3
 
 /* GEMM tile constants the packed-weight layout depends on */
 #define FVIT_TILE_N 128 /* weight rows are zero-padded to a multiple of this */
@@ -163,7 +166,7 @@ typedef struct FvitStageTables {
 typedef struct FvitMapView {
     void* data;
     int64_t stride_b, stride_c, stride_h, stride_w;
-    int32_t dtype; /* FVIT_F32 / FVIT_F16 / FVIT_BF16 */
+    int32_t dtype; /* FVIT_F32 / FVIT_F16 / FVIT_BF16; FVIT_U8 for the image of a fvit_*_u8 entry point */
     int32_t _pad;
 } FvitMapView;
 
@@ -605,6 +608,25 @@ int fvit_stem_conv3x3s2(int32_t dtype, const FvitMapView* in, const void* weight
  * H1 = (Hi-1)/2+1, H2 = (H1-1)/2+1 (same for W). */
 int fvit_stem_fused(int32_t dtype, const FvitMapView* in, const void* w1, const float* b1, const void* w2, const float* b2,
                     void* out, int32_t B, int32_t Hi, int32_t Wi, fvit_stream_t stream);
+
+/* ---- uint8 images.  The three stem entry points above with a FVIT_U8 view of the (B, 3, Hi, Wi) image and
+ * norm = scale[3] followed by shift[3] in HOST memory (read at the call and passed by value: no device allocation, no copy, capturable):
+ * every gathered byte u of channel c becomes fmaf((float)u, scale[c], shift[c]), a tap outside the image 0 (the padding follows the
+ * normalisation).  With scale[c] = fp32(1 / (255 std[c])) and shift[c] = fp32(-mean[c] / std[c]) the result is bit for bit the float entry
+ * point's on the fp32 image normalised by that formula in the same memory layout.  fvit_stem_fused_u8 has a second gather for the decoder's
+ * HWC layout (stride_c 1, stride_w 3, stride_h 3 Wi; tune key stem_nhwc3 as for fp32).  A FVIT_U8 view given to the float entry points, or
+ * any other view given to these, is FVIT_EINVAL: the image bytes are never read as another type. */
+int fvit_stem_conv3x3s2_u8(int32_t dtype, const FvitMapView* in, const void* weight, const float* bias, void* out,
+                           int32_t B, int32_t Hi, int32_t Wi, fvit_stream_t stream, const float* norm);
+int fvit_stem_conv3x3s2_px_u8(int32_t dtype, const FvitMapView* in, const void* weight, const void* weight_lo, const float* bias, void* out,
+                              int32_t B, int32_t Hi, int32_t Wi, fvit_stream_t stream, const float* norm);
+int fvit_stem_fused_u8(int32_t dtype, const FvitMapView* in, const void* w1, const float* b1, const void* w2, const float* b2,
+                       void* out, int32_t B, int32_t Hi, int32_t Wi, fvit_stream_t stream, const float* norm);
+/* The same normalisation as a pass of its own, for every route the fused stems do not cover: in = FVIT_U8 view of (B, C, H, W), any strides,
+ * C <= 16; out = dense fp32, [B][C][H][W] (channels_last = 0) or [B][H][W][C] (1); norm = scale[C] then shift[C] in host
+ * memory; mask = optional [B][H][W] bytes, non-zero = padded pixel, written as 0 (DINO pads after normalising). */
+int fvit_image_normalize_u8(const FvitMapView* in, float* out, int32_t channels_last, int32_t B, int32_t C, int32_t H, int32_t W,
+                            const float* norm, const void* mask, fvit_stream_t stream);
 
 /* ---- backward of the MLP sub-block  y = x + gamma * fc2(GELU(fc1(LayerNorm(x))))  (Mlp.forward FV:398-407 inside HAT.forward FV:691; the reference
  * differentiates it with autograd, train.py:820-951) -- SURVEY.md section 8 row f-4, the slice VERDICT r02 item 9 scopes (csrc/fvit_bwd.hip).

@@ -8,7 +8,7 @@ optional gather of the logits to rank 0 (--gather-logits, for parity checks).
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 scripts/run_sharded_validate.py ...
 
 Data: --synthetic N (seeded randn images + random labels, the same stream of samples whatever the number of ranks) or
---tensors FILE.pt (a dict with 'images' (N,3,H,W) and 'labels' (N,)).  Each rank evaluates samples
+--tensors FILE.pt (a dict with 'images' (N,3,H,W), already normalised floats or raw uint8, and 'labels' (N,)).  Each rank evaluates samples
 [shard_bounds(N, world, rank)) in batches of -b through ``model.compile_inference`` (deploy plan + stream shards in one hipGraph);
 --eager runs ``model(x)`` (under autocast with --amp) instead.
 """
@@ -61,7 +61,8 @@ class ShardLoader:
         for s in range(self.lo, self.hi, self.batch):
             e = min(s + self.batch, self.hi)
             if self.tensors is not None:
-                yield self.tensors["images"][s:e].float(), self.tensors["labels"][s:e].long()
+                img = self.tensors["images"][s:e]   # uint8 images stay uint8: the model / runner normalises them on the GPU (set_input_norm)
+                yield (img if img.dtype == torch.uint8 else img.float()), self.tensors["labels"][s:e].long()
             else:
                 xs, ys = zip(*(self._sample(i) for i in range(s, e)))
                 yield torch.stack(xs), torch.tensor(ys, dtype=torch.int64)
