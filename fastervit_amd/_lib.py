@@ -44,6 +44,7 @@ EXPORTED_SYMBOLS = (
     "fvit_hat_stage_forward_tail", "fvit_rows_avgpool", "fvit_conv3x3_c64_ln2d", "fvit_conv3x3_c128_band_ln2d",
     "fvit_conv3x3", "fvit_conv3x3_route", "fvit_conv3x3_route_name",
     "fvit_stem_conv3x3s2_u8", "fvit_stem_conv3x3s2_px_u8", "fvit_stem_fused_u8", "fvit_image_normalize_u8",
+    "fvit_msda_forward", "fvit_msda_backward",
 )
 # only in libfvit_hip_diag.so (the same sources with -DFVIT_DIAG; FVIT_DIAG=1 selects it): diagnosis entry points of include/fvit_hip.h's #ifdef FVIT_DIAG
 # section.  The shipped library exports none of them and compiles the ablation knobs out (tests/test_abi.py).
@@ -263,6 +264,11 @@ def _declare(lib):
     lib.fvit_stem_fused_u8.argtypes = list(lib.fvit_stem_fused.argtypes) + [fp]
     lib.fvit_image_normalize_u8.restype = C.c_int
     lib.fvit_image_normalize_u8.argtypes = [C.POINTER(FvitMapView), vp, i32, i32, i32, i32, i32, fp, vp, vp]
+    # multi-scale deformable attention (ops.py): dtype, value, shapes, starts, loc, attn, ... , N, S, M, D, Lq, L, P, stream
+    lib.fvit_msda_forward.restype = C.c_int
+    lib.fvit_msda_forward.argtypes = [i32, vp, vp, vp, vp, vp, vp] + [i32] * 7 + [vp]
+    lib.fvit_msda_backward.restype = C.c_int
+    lib.fvit_msda_backward.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp] + [i32] * 7 + [vp]
     lib.fvit_head_logits.restype = C.c_int
     lib.fvit_head_logits.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
     lib.fvit_head_softmax_xent.restype = C.c_int

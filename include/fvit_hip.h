@@ -694,6 +694,28 @@ int fvit_head_grad(const float* dlogits, const float* feat, const float* loss_ro
 int fvit_sgd_momentum(float* param, float* momentum, const float* grad, int64_t n, float lr, float mu, float weight_decay,
                       fvit_stream_t stream);
 
+/* ---- multi-scale deformable attention (Deformable DETR / DINO MSDeformAttnFunction; csrc/fvit_msda.hip) ----
+ *   out[n][q][m][:] = sum over l < L, p < P of  attention_weights[n][q][m][l][p] * bilinear(value_l[n][:][m][:], sampling_locations[n][q][m][l][p])
+ * with the semantics of the reference's ms_deform_attn_core_pytorch: align_corners = False, zero padding, pixel coordinate x = loc_x * W - 0.5 and
+ * y = loc_y * H - 0.5, loc = (x, y) in [0, 1].  All tensors dense, in device memory:
+ *   value                T [N][S][M][D]         T = value_dtype: FVIT_F32, FVIT_F16 or FVIT_BF16; level l is rows level_start_index[l] .. + H_l * W_l - 1
+ *   spatial_shapes       int64 [L][2] = (H, W);  level_start_index  int64 [L]   (read by the kernels, never by the host; a sample whose row would fall
+ *                                                                                outside the S rows contributes nothing)
+ *   sampling_locations   f32 [N][Lq][M][L][P][2];  attention_weights  f32 [N][Lq][M][L][P]
+ *   out                  T [N][Lq][M * D]       fp32 accumulation in a fixed order, rounded once (fp16 saturates): bitwise repeatable
+ * D = 16, 32, 64 or 128, L <= 8, P <= 16; anything else, and any other dtype code, is refused with FVIT_EINVAL before a launch.  value,
+ * sampling_locations, out and grad_sampling_loc must be 8-byte aligned.  No allocation and no host synchronisation: both calls can be captured into a graph. */
+int fvit_msda_forward(int32_t value_dtype, const void* value, const int64_t* spatial_shapes, const int64_t* level_start_index,
+                      const float* sampling_locations, const float* attention_weights, void* out, int32_t N, int32_t S, int32_t M, int32_t D,
+                      int32_t Lq, int32_t L, int32_t P, fvit_stream_t stream);
+/* The three gradients from grad_out (T [N][Lq][M * D]).  grad_sampling_loc (f32, sampling_locations' shape) and grad_attn_weight (f32, attention_weights'
+ * shape) are written in full, one fixed-order sum over D each: bitwise repeatable.  grad_value is f32 [N][S][M][D] for every T: the call zero-fills it on
+ * `stream` and scatter-adds into it with float atomics, so its last bits depend on the arrival order of the adds; a 16-bit caller rounds it once afterwards. */
+int fvit_msda_backward(int32_t value_dtype, const void* value, const int64_t* spatial_shapes, const int64_t* level_start_index,
+                       const float* sampling_locations, const float* attention_weights, const void* grad_out, float* grad_value,
+                       float* grad_sampling_loc, float* grad_attn_weight, int32_t N, int32_t S, int32_t M, int32_t D, int32_t Lq, int32_t L, int32_t P,
+                       fvit_stream_t stream);
+
 /* Performance-experiment knobs for A/B runs inside one process; the same keys can be preset through the environment as
  * FVIT_TUNE_<key>=<int> (read once per key).  Kernel-selection knobs never change results beyond fp32 summation order:
  *   "mlp_fused", "attn_fused" 0/1; "mlp_fused_min_rows", "attn_fused_min_rows", "mlp_fused512_min_rows", "attn_fused512_min_rows";
