@@ -9,6 +9,7 @@ ABI of ``include/fvit_hip.h``; the conv side is PyTorch-ROCm.  See DESIGN.md / I
 from .models import create_model, list_models, is_model, model_entrypoint  # noqa: F401
 from .models import FasterViTBackbone, build_fastervit  # noqa: F401  (multi-scale detection backbone)
 from .ops import MSDeformAttn, MSDeformAttnFunction, ms_deform_attn  # noqa: F401  (multi-scale deformable attention of the DINO heads)
+from .preprocess import ClassifierPreprocess, DetectionPreprocess, NestedTensor, resize_batch  # noqa: F401  (decoded uint8 images -> uint8 batch, on the GPU)
 from .models.registry import load_checkpoint, load_state_dict, register_pip_model  # noqa: F401
 
 __version__ = "0.1.0"

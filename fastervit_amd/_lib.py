@@ -45,7 +45,11 @@ EXPORTED_SYMBOLS = (
     "fvit_conv3x3", "fvit_conv3x3_route", "fvit_conv3x3_route_name",
     "fvit_stem_conv3x3s2_u8", "fvit_stem_conv3x3s2_px_u8", "fvit_stem_fused_u8", "fvit_image_normalize_u8",
     "fvit_msda_forward", "fvit_msda_backward",
+    "fvit_image_resize_check", "fvit_image_resize_u8",
 )
+FVIT_RESIZE_BILINEAR, FVIT_RESIZE_BICUBIC = 1, 2
+# fvit_image_resize_check's reason codes
+FVIT_RESIZE_REASONS = {-16: "size", -17: "filter", -18: "window", -19: "slot", -20: "stride", -21: "tap limit", -22: "LDS limit"}
 # only in libfvit_hip_diag.so (the same sources with -DFVIT_DIAG; FVIT_DIAG=1 selects it): diagnosis entry points of include/fvit_hip.h's #ifdef FVIT_DIAG
 # section.  The shipped library exports none of them and compiles the ablation knobs out (tests/test_abi.py).
 DIAG_SYMBOLS = (
@@ -93,6 +97,11 @@ class FvitStageTail(C.Structure):
 class FvitMapView(C.Structure):
     _fields_ = [("data", C.c_void_p), ("stride_b", C.c_int64), ("stride_c", C.c_int64), ("stride_h", C.c_int64),
                 ("stride_w", C.c_int64), ("dtype", C.c_int32), ("_pad", C.c_int32)]
+
+
+class FvitResizeDesc(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("row_stride", C.c_int64)] + \
+               [(n, C.c_int32) for n in ("H", "W", "rh", "rw", "top", "left", "ch", "cw", "filter", "_pad")]
 
 
 class FvitConvWeights(C.Structure):
@@ -269,6 +278,11 @@ def _declare(lib):
     lib.fvit_msda_forward.argtypes = [i32, vp, vp, vp, vp, vp, vp] + [i32] * 7 + [vp]
     lib.fvit_msda_backward.restype = C.c_int
     lib.fvit_msda_backward.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp] + [i32] * 7 + [vp]
+    # resize + crop + pad of decoded uint8 images (preprocess.py): host descriptor query; device descriptors, B, out view, Ho, Wo, fill, mask, stream
+    lib.fvit_image_resize_check.restype = C.c_int
+    lib.fvit_image_resize_check.argtypes = [C.POINTER(FvitResizeDesc), i32, i32]
+    lib.fvit_image_resize_u8.restype = C.c_int
+    lib.fvit_image_resize_u8.argtypes = [vp, i32, C.POINTER(FvitMapView), i32, i32, i32, vp, vp]
     lib.fvit_head_logits.restype = C.c_int
     lib.fvit_head_logits.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
     lib.fvit_head_softmax_xent.restype = C.c_int

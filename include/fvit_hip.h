@@ -716,6 +716,39 @@ int fvit_msda_backward(int32_t value_dtype, const void* value, const int64_t* sp
                        float* grad_sampling_loc, float* grad_attn_weight, int32_t N, int32_t S, int32_t M, int32_t D, int32_t Lq, int32_t L, int32_t P,
                        fvit_stream_t stream);
 
+/* ---- resize + crop + pad of decoded uint8 images into a uint8 batch (csrc/fvit_resize.hip) ----
+ * One launch for B images of different sizes.  Image i: H x W x 3 uint8 pixels in HWC order at src, rows row_stride bytes apart, resized to rh x rw with
+ * PIL's Image.resize semantics for 8-bit images (separable, horizontal pass first, each pass rounded and clamped to uint8, an axis of unchanged size
+ * skipped; antialiased: the support grows with the downscale), of which the window (top, left, ch, cw) is written at the top-left corner of slot i of the
+ * (B, 3, Ho, Wo) destination; every other pixel of the slot gets `fill`.  mask, when given, is [B][Ho][Wo] bytes: 0 on the window, 1 elsewhere. */
+#define FVIT_RESIZE_BILINEAR 1 /* triangle, radius 1 */
+#define FVIT_RESIZE_BICUBIC 2  /* Keys cubic with a = -0.5 (PIL's), radius 2 */
+/* why a descriptor is refused (fvit_image_resize_check) */
+#define FVIT_RESIZE_ESIZE (-16)   /* H, W, rh, rw, ch or cw < 1 */
+#define FVIT_RESIZE_EFILTER (-17) /* unknown filter code */
+#define FVIT_RESIZE_EWINDOW (-18) /* the window does not lie inside the resized image */
+#define FVIT_RESIZE_ESLOT (-19)   /* the window is larger than the Ho x Wo slot */
+#define FVIT_RESIZE_ESTRIDE (-20) /* row_stride < 3 W */
+#define FVIT_RESIZE_ETAPS (-21)   /* more than 66 taps per output: a downscale beyond 16x (bicubic) / 32x (bilinear) on one axis */
+#define FVIT_RESIZE_ELDS (-22)    /* the source rows of one 8-row output tile exceed the kernel's 192-row LDS image (bilinear beyond 21.2x vertically) */
+typedef struct FvitResizeDesc {
+    const void* src;    /* device pointer, H x W x 3 uint8, HWC */
+    int64_t row_stride; /* bytes, >= 3 W */
+    int32_t H, W;       /* source size */
+    int32_t rh, rw;     /* resized size */
+    int32_t top, left, ch, cw; /* the output window inside the resized image */
+    int32_t filter;     /* FVIT_RESIZE_BILINEAR / FVIT_RESIZE_BICUBIC */
+    int32_t _pad;
+} FvitResizeDesc;
+/* 0, or the FVIT_RESIZE_E* code (message in fvit_last_error) for ONE descriptor in HOST memory and a slot of Ho x Wo; src is not examined.  No device call. */
+int fvit_image_resize_check(const FvitResizeDesc* desc, int32_t Ho, int32_t Wo);
+/* descs = B descriptors in DEVICE memory, owned by the caller and read by the kernel alone: the call allocates nothing, copies nothing and does not
+ * synchronise, so it can be captured, and a replay follows the descriptors and source bytes of that moment.  The kernel applies the check above to each
+ * descriptor itself: one it would refuse (or a null src) turns its slot into fill + mask 1.  out = a FVIT_U8 view of the (B, 3, Ho, Wo) destination with
+ * positive byte strides (planar, channels-last or a slice of either); fill in 0 .. 255; mask device pointer or NULL.  Bitwise repeatable (no atomics). */
+int fvit_image_resize_u8(const FvitResizeDesc* descs, int32_t B, const FvitMapView* out, int32_t Ho, int32_t Wo, int32_t fill, void* mask,
+                         fvit_stream_t stream);
+
 /* Performance-experiment knobs for A/B runs inside one process; the same keys can be preset through the environment as
  * FVIT_TUNE_<key>=<int> (read once per key).  Kernel-selection knobs never change results beyond fp32 summation order:
  *   "mlp_fused", "attn_fused" 0/1; "mlp_fused_min_rows", "attn_fused_min_rows", "mlp_fused512_min_rows", "attn_fused512_min_rows";
