@@ -46,7 +46,9 @@ EXPORTED_SYMBOLS = (
     "fvit_stem_conv3x3s2_u8", "fvit_stem_conv3x3s2_px_u8", "fvit_stem_fused_u8", "fvit_image_normalize_u8",
     "fvit_msda_forward", "fvit_msda_backward",
     "fvit_image_resize_check", "fvit_image_resize_u8",
+    "fvit_det_select", "fvit_box_nms_workspace", "fvit_box_nms", "fvit_box_pairwise", "fvit_det_matcher_cost",
 )
+FVIT_BOX_IOU, FVIT_BOX_GIOU = 0, 1
 FVIT_RESIZE_BILINEAR, FVIT_RESIZE_BICUBIC = 1, 2
 # fvit_image_resize_check's reason codes
 FVIT_RESIZE_REASONS = {-16: "size", -17: "filter", -18: "window", -19: "slot", -20: "stride", -21: "tap limit", -22: "LDS limit"}
@@ -283,6 +285,17 @@ def _declare(lib):
     lib.fvit_image_resize_check.argtypes = [C.POINTER(FvitResizeDesc), i32, i32]
     lib.fvit_image_resize_u8.restype = C.c_int
     lib.fvit_image_resize_u8.argtypes = [vp, i32, C.POINTER(FvitMapView), i32, i32, i32, vp, vp]
+    # detection post-processing (detection_ops.py): select + decode, NMS and its workspace query, pairwise IoU / GIoU, the matcher's cost
+    lib.fvit_det_select.restype = C.c_int
+    lib.fvit_det_select.argtypes = [vp] * 7 + [i32] * 6 + [vp]
+    lib.fvit_box_nms_workspace.restype = C.c_size_t
+    lib.fvit_box_nms_workspace.argtypes = [i32, i32]
+    lib.fvit_box_nms.restype = C.c_int
+    lib.fvit_box_nms.argtypes = [vp, vp, vp, f32, vp, vp, vp, C.c_size_t, i32, i32, vp]
+    lib.fvit_box_pairwise.restype = C.c_int
+    lib.fvit_box_pairwise.argtypes = [i32, vp, vp, vp, vp, i32, i32, vp]
+    lib.fvit_det_matcher_cost.restype = C.c_int
+    lib.fvit_det_matcher_cost.argtypes = [vp] * 5 + [i32] * 3 + [f32] * 4 + [vp]
     lib.fvit_head_logits.restype = C.c_int
     lib.fvit_head_logits.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
     lib.fvit_head_softmax_xent.restype = C.c_int

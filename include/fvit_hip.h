@@ -749,6 +749,41 @@ int fvit_image_resize_check(const FvitResizeDesc* desc, int32_t Ho, int32_t Wo);
 int fvit_image_resize_u8(const FvitResizeDesc* descs, int32_t B, const FvitMapView* out, int32_t Ho, int32_t Wo, int32_t fill, void* mask,
                          fvit_stream_t stream);
 
+/* ---- detection post-processing (csrc/fvit_boxes.hip) ----
+ * Everything below is fp32, dense, in device memory; no call allocates, synchronises or reads device data on the host, so each can be captured into a
+ * graph; no output is written with atomics, so each is bitwise repeatable.  Box arrays must be 16-byte aligned.
+ *
+ * DINO's PostProcess without NMS: the K highest of the Q * C logits of every image in descending order, ties to the lower flat index q * C + c, NaN
+ * above +inf (torch.topk's rank); the selection runs on the logits and only the winners go through the sigmoid.
+ *   logits f32 [B][Q][C]; boxes f32 [B][Q][4] cxcywh; target_sizes f32 [B][2] = (h, w)
+ *   scores f32 [B][K] = sigmoid(logit); labels i64 [B][K] = c; query i64 [B][K] = q; out_boxes f32 [B][K][4] =
+ *   (xc - 0.5 w, yc - 0.5 h, xc + 0.5 w, yc + 0.5 h) (the box as it is with not_to_xyxy; with test, x1 - x0 and y1 - y0 in the last two) times (w, h, w, h)
+ *   of target_sizes: bit for bit the reference's fp32 arithmetic.
+ * Refused by name (FVIT_EINVAL) before a launch: B < 1, K outside 1 .. min(1024, Q * C), Q * C >= 2^24, test together with not_to_xyxy. */
+int fvit_det_select(const float* logits, const float* boxes, const float* target_sizes, float* scores, int64_t* labels, int64_t* query, float* out_boxes,
+                    int32_t B, int32_t Q, int32_t C, int32_t K, int32_t not_to_xyxy, int32_t test, fvit_stream_t stream);
+/* NMS by torchvision's rule on G independent groups of N boxes (xyxy).  order i64 [G][N] lists each group's boxes by descending score (NULL: the boxes are
+ * already in that order); box order[j] is kept iff no earlier KEPT box i has inter / (area_i + area_j - inter) > iou_threshold, with
+ * inter = max(0, min x2 - max x1) * max(0, min y2 - max y1): no epsilon, no +1 pixel, strict >, and 0 / 0 = NaN compares false.  idxs i64 [G][N] (or NULL):
+ * class ids, a pair with different ids never suppresses (batched_nms).  keep i64 [G][N]: the kept original indices in score order, then -1; count i32 [G].
+ * workspace: at least the byte count of the workspace query below (8-byte aligned; 0 from the query = unsupported sizes).
+ * N <= 8192; N == 0 returns FVIT_OK without a launch and writes nothing. */
+size_t fvit_box_nms_workspace(int32_t G, int32_t N);
+int fvit_box_nms(const float* boxes, const int64_t* order, const int64_t* idxs, float iou_threshold, int64_t* keep, int32_t* count, void* workspace,
+                 size_t workspace_bytes, int32_t G, int32_t N, fvit_stream_t stream);
+/* Pairwise box_iou / generalized_box_iou of the reference's util/box_ops.py (xyxy, 1e-6 added to the union and to the enclosing area in the quotients):
+ * boxes1 [N][4] x boxes2 [M][4] -> out [N][M]; FVIT_BOX_IOU also writes the union to union_out [N][M] when it is not NULL. */
+#define FVIT_BOX_IOU 0
+#define FVIT_BOX_GIOU 1
+int fvit_box_pairwise(int32_t mode, const float* boxes1, const float* boxes2, float* out, float* union_out, int32_t N, int32_t M, fvit_stream_t stream);
+/* The Hungarian matcher's cost matrix (reference matcher.py, gamma = 2): cost [R][T] =
+ *   cost_bbox * L1(pred, tgt) + cost_class * (pos - neg)[r][tgt_ids[t]] - cost_giou * GIoU(xyxy(pred), xyxy(tgt)),
+ * p = sigmoid(logits [R][C]), neg = (1 - alpha) p^2 (-log(1 - p + 1e-8)), pos = alpha (1 - p)^2 (-log(p + 1e-8)), evaluated only at the T gathered classes
+ * of each row; pred_boxes [R][4] and tgt_boxes [T][4] cxcywh; tgt_ids i64 [T].  A tgt_ids entry outside [0, C) makes its column NaN; nothing is read
+ * out of bounds. */
+int fvit_det_matcher_cost(const float* logits, const float* pred_boxes, const int64_t* tgt_ids, const float* tgt_boxes, float* cost, int32_t R, int32_t C,
+                          int32_t T, float cost_class, float cost_bbox, float cost_giou, float focal_alpha, fvit_stream_t stream);
+
 /* Performance-experiment knobs for A/B runs inside one process; the same keys can be preset through the environment as
  * FVIT_TUNE_<key>=<int> (read once per key).  Kernel-selection knobs never change results beyond fp32 summation order:
  *   "mlp_fused", "attn_fused" 0/1; "mlp_fused_min_rows", "attn_fused_min_rows", "mlp_fused512_min_rows", "attn_fused512_min_rows";
