@@ -47,7 +47,9 @@ EXPORTED_SYMBOLS = (
     "fvit_msda_forward", "fvit_msda_backward",
     "fvit_image_resize_check", "fvit_image_resize_u8",
     "fvit_det_select", "fvit_box_nms_workspace", "fvit_box_nms", "fvit_box_pairwise", "fvit_det_matcher_cost",
+    "fvit_det_label_loss_workspace", "fvit_det_label_loss", "fvit_det_label_loss_backward", "fvit_det_box_loss", "fvit_det_box_loss_backward",
 )
+FVIT_DET_MAX_SETS = 16
 FVIT_BOX_IOU, FVIT_BOX_GIOU = 0, 1
 FVIT_RESIZE_BILINEAR, FVIT_RESIZE_BICUBIC = 1, 2
 # fvit_image_resize_check's reason codes
@@ -104,6 +106,14 @@ class FvitMapView(C.Structure):
 class FvitResizeDesc(C.Structure):
     _fields_ = [("src", C.c_void_p), ("row_stride", C.c_int64)] + \
                [(n, C.c_int32) for n in ("H", "W", "rh", "rw", "top", "left", "ch", "cw", "filter", "_pad")]
+
+
+class FvitDetLabelSet(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("logits", "classes", "targets", "grad_logits")] + [(n, C.c_int32) for n in ("R", "Q", "B")] + [("scale", C.c_float)]
+
+
+class FvitDetBoxSet(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("src", "tgt", "grad_src")] + [("M", C.c_int32), ("scale", C.c_float)]
 
 
 class FvitConvWeights(C.Structure):
@@ -296,6 +306,18 @@ def _declare(lib):
     lib.fvit_box_pairwise.argtypes = [i32, vp, vp, vp, vp, i32, i32, vp]
     lib.fvit_det_matcher_cost.restype = C.c_int
     lib.fvit_det_matcher_cost.argtypes = [vp] * 5 + [i32] * 3 + [f32] * 4 + [vp]
+    # the training criterion (criterion.py): host tables of set descriptors; label loss (sets, n, C, alpha, gamma, loss, card, card_stride, hits,
+    # workspace, bytes, stream), its backward (.., grad_loss, stream), box loss (sets, n, out, stream) and its backward (sets, n, grad_out, stream)
+    lib.fvit_det_label_loss_workspace.restype = C.c_size_t
+    lib.fvit_det_label_loss_workspace.argtypes = [C.POINTER(FvitDetLabelSet), i32, i32]
+    lib.fvit_det_label_loss.restype = C.c_int
+    lib.fvit_det_label_loss.argtypes = [C.POINTER(FvitDetLabelSet), i32, i32, f32, f32, vp, vp, i32, vp, vp, C.c_size_t, vp]
+    lib.fvit_det_label_loss_backward.restype = C.c_int
+    lib.fvit_det_label_loss_backward.argtypes = [C.POINTER(FvitDetLabelSet), i32, i32, f32, f32, vp, vp]
+    lib.fvit_det_box_loss.restype = C.c_int
+    lib.fvit_det_box_loss.argtypes = [C.POINTER(FvitDetBoxSet), i32, vp, vp]
+    lib.fvit_det_box_loss_backward.restype = C.c_int
+    lib.fvit_det_box_loss_backward.argtypes = [C.POINTER(FvitDetBoxSet), i32, vp, vp]
     lib.fvit_head_logits.restype = C.c_int
     lib.fvit_head_logits.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
     lib.fvit_head_softmax_xent.restype = C.c_int

@@ -10,8 +10,8 @@ Drop-ins, by signature and result, for what the reference's detection code takes
     PostProcess(num_select, nms_iou_threshold)                          the reference's list of dicts; postprocess_launch is its capturable form
     HungarianMatcher(cost_class, cost_bbox, cost_giou, focal_alpha)     the cost matrix from one kernel, one copy to the host, scipy imported lazily
 
-The pairwise ops are forward only: an input that requires grad while grad mode is on raises (the differentiable GIoU of the losses is not part of this
-library).  The reference's ``generalized_box_iou`` asserts ``(boxes[:, 2:] >= boxes[:, :2]).all()``, a host synchronisation per call; it is deliberately
+The pairwise ops are forward only: an input that requires grad while grad mode is on raises (the differentiable GIoU of the losses, over matched pairs,
+lives in criterion.py).  The reference's ``generalized_box_iou`` asserts ``(boxes[:, 2:] >= boxes[:, :2]).all()``, a host synchronisation per call; it is deliberately
 not kept: a degenerate box gives the value the formula gives.  16-bit inputs are widened to fp32 here and results narrowed back once; float64 is refused
 by name; a CPU tensor raises (there is no CPU or eager fallback).  Ties in the top-k go to the lower flat index ``q * C + c``.
 """

@@ -784,6 +784,55 @@ int fvit_box_pairwise(int32_t mode, const float* boxes1, const float* boxes2, fl
 int fvit_det_matcher_cost(const float* logits, const float* pred_boxes, const int64_t* tgt_ids, const float* tgt_boxes, float* cost, int32_t R, int32_t C,
                           int32_t T, float cost_class, float cost_bbox, float cost_giou, float focal_alpha, fvit_stream_t stream);
 
+/* ---- the DINO training criterion (csrc/fvit_loss.hip) ----
+ * The same rules as above: fp32, dense, device memory; nothing is allocated, no host synchronisation, capturable; no float atomic on any output, every
+ * reduction runs in a fixed order, so every result is bitwise repeatable.  The descriptor tables are HOST memory, read during the call (a captured
+ * graph keeps the pointers and sizes of that moment).  Up to FVIT_DET_MAX_SETS output sets (decoder layers, interm, denoising sets) per call.
+ *
+ * Label loss of set s (reference SetCriterion.loss_labels + loss_cardinality + accuracy, without the one-hot tensor):
+ *   loss[s]  = scale * sum_{r, c} alpha_t * ce * (1 - p_t)^gamma, ce the stable BCE with logits, p = sigmoid(x), t = [c == classes[r]] (or targets[r][c]
+ *              != 0 when the dense targets are given); alpha < 0: no alpha weighting; gamma == 2 is specialised.  scale = 1 / num_boxes gives the
+ *              reference's loss.mean(1).sum() / num_boxes * Q.
+ *   card[s * card_stride + b] = rows r of image b (r / Q == b) whose argmax over c is not C - 1, ties to the lowest c (int32; card_stride >= every B)
+ *   hits[s]  = rows with classes[r] < C whose argmax equals classes[r] (int32; 0 with dense targets)
+ * A classes value outside [0, C] makes loss[s] NaN (and that row's gradient); nothing is read or written out of bounds.
+ * Reduction: per workgroup (image b, a chunk of rows) at most 32 sequential additions per lane, 6 in the wave, 2 across the 4 waves; then one wave
+ * per set adds ceil(P / 64) - 1 partials per lane and 6 in the wave (P = B * chunks workgroups), and multiplies by scale. */
+#define FVIT_DET_MAX_SETS 16
+typedef struct FvitDetLabelSet {
+    const float* logits;    /* [R][C] */
+    const int32_t* classes; /* [R], values in [0, C], C = no object; may be NULL when targets is given */
+    const float* targets;   /* NULL, or dense 0 / 1 targets [R][C] (sigmoid_focal_loss) */
+    float* grad_logits;     /* [R][C]: written by fvit_det_label_loss_backward only */
+    int32_t R, Q, B;        /* R = B * Q */
+    float scale;
+} FvitDetLabelSet;
+/* bytes of workspace fvit_det_label_loss needs for these sets (16-byte aligned); 0 = refused, message in fvit_last_error */
+size_t fvit_det_label_loss_workspace(const FvitDetLabelSet* sets, int32_t n_sets, int32_t C);
+int fvit_det_label_loss(const FvitDetLabelSet* sets, int32_t n_sets, int32_t C, float alpha, float gamma, float* loss, int32_t* card,
+                        int32_t card_stride, int32_t* hits, void* workspace, size_t workspace_bytes, fvit_stream_t stream);
+/* grad_logits[r][c] = grad_loss[s] * scale * d(sum) / d(logits[r][c]), recomputed from the logits; grad_loss f32 [n_sets] is DEVICE memory. */
+int fvit_det_label_loss_backward(const FvitDetLabelSet* sets, int32_t n_sets, int32_t C, float alpha, float gamma, const float* grad_loss,
+                                 fvit_stream_t stream);
+/* Box loss of set s over M matched pairs (reference SetCriterion.loss_boxes), src and tgt [M][4] cxcywh, 16-byte aligned:
+ *   out[s][0] = scale * sum (|dcx| + |dcy|)   (loss_xy)      out[s][1] = scale * sum (|dw| + |dh|)   (loss_hw)
+ *   out[s][2] = scale * sum (1 - GIoU(xyxy(src), xyxy(tgt))), 1e-6 in both quotients (loss_giou)      out[s][3] = out[s][0] + out[s][1]   (loss_bbox)
+ * One workgroup per set: ceil(M / 256) pairs per lane in sequence, 6 additions in the wave, 2 across the waves.  A set with M == 0 gives zeros; when
+ * EVERY set has M == 0 nothing is launched and nothing is written.
+ * Backward: grad_src[i] = scale * ((g[s][0] + g[s][3]) sign(d) on cx, cy; (g[s][1] + g[s][3]) sign(d) on w, h; + g[s][2] d(1 - GIoU) / d(src)), sign(0) = 0,
+ * a tie of a max / min splits its gradient in halves and a clamp passes it at 0 (torch's rules); grad_out f32 [n_sets][4] is DEVICE memory. */
+typedef struct FvitDetBoxSet {
+    const float* src;   /* [M][4] */
+    const float* tgt;   /* [M][4] */
+    float* grad_src;    /* [M][4]: written by fvit_det_box_loss_backward only */
+    int32_t M;
+    float scale;
+} FvitDetBoxSet;
+int fvit_det_box_loss(const FvitDetBoxSet* sets, int32_t n_sets, float* out, fvit_stream_t stream);
+int fvit_det_box_loss_backward(const FvitDetBoxSet* sets, int32_t n_sets, const float* grad_out, fvit_stream_t stream);
+/* Refused by name (FVIT_EINVAL) before any launch, outputs untouched: n_sets outside 1 .. 16, C < 1, R < 1 or R != B * Q, R * C >= 2^31, M < 0,
+ * card_stride < B, a null or misaligned pointer (floats and ints 4 bytes, boxes and the workspace 16 bytes); FVIT_EWORKSPACE for a short workspace. */
+
 /* Performance-experiment knobs for A/B runs inside one process; the same keys can be preset through the environment as
  * FVIT_TUNE_<key>=<int> (read once per key).  Kernel-selection knobs never change results beyond fp32 summation order:
  *   "mlp_fused", "attn_fused" 0/1; "mlp_fused_min_rows", "attn_fused_min_rows", "mlp_fused512_min_rows", "attn_fused512_min_rows";
