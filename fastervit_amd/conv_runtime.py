@@ -50,14 +50,6 @@ from . import _lib, hat_runtime
 _CODE = {torch.float16: _lib.FVIT_F16, torch.bfloat16: _lib.FVIT_BF16}
 
 
-def _stream(device=None):
-    return torch.cuda.current_stream(device).cuda_stream
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
-
-
 def _bn_scale_shift(bn):
     s = bn.weight.float() / torch.sqrt(bn.running_var.float() + bn.eps)
     t = bn.bias.float() - bn.running_mean.float() * s
@@ -101,7 +93,7 @@ class ConvWeight(NamedTuple):
     def images(self) -> _lib.FvitConvWeights:
         """Every packed image for the conv driver (``fvit_conv3x3``): ``wk`` is the dense image when ``wk_classic`` is set, the classic one otherwise."""
         classic, dense = (self.wk, None) if self.wk_classic is None else (self.wk_classic, self.wk)
-        return _lib.FvitConvWeights(_ptr(classic), _ptr(dense), _ptr(self.wband), self.terms, self.cv)
+        return _lib.FvitConvWeights(_lib.ptr(classic), _lib.ptr(dense), _lib.ptr(self.wband), self.terms, self.cv)
 
 
 # the entries of ``DeployPlan.t`` (``_build``); biases and LayerNorm2d parameters are fp32, zero-padded to the map layout
@@ -236,13 +228,14 @@ class DeployPlan:
         runs the plain conv.  Returns whether the LayerNorm2d was applied."""
         B, Ci, Hi, Wi = x.shape
         lib, wts = _lib.lib(), w.images()
-        call = _lib.FvitConvCall(x.data_ptr(), _ptr(x_lo), _ptr(bias), _ptr(res), _ptr(res_lo), _ptr(out), _ptr(out_lo), _ptr(out_f32), None, None,
+        ptr = _lib.ptr
+        call = _lib.FvitConvCall(x.data_ptr(), ptr(x_lo), ptr(bias), ptr(res), ptr(res_lo), ptr(out), ptr(out_lo), ptr(out_f32), None, None,
                                  self._zero_page(x.device), 0.0, B, Hi, Wi, Ci, w.wk.shape[0], stride, act, int(px))
         if ln is not None:
             call.ln_w, call.ln_b, call.ln_eps = ln.ln_w.data_ptr(), ln.ln_b.data_ptr(), ln.eps
             if not lib.fvit_conv3x3_route_name(lib.fvit_conv3x3_route(self.code, wts, call)).endswith(b"<ln>"):
                 call.ln_w = call.ln_b = ln = None
-        _lib.check(lib.fvit_conv3x3(self.code, wts, call, _stream(self.dev)), "fvit_conv3x3")
+        _lib.check(lib.fvit_conv3x3(self.code, wts, call, _lib.stream_ptr(self.dev)), "fvit_conv3x3")
         return ln is not None
 
     def _conv(self, x, w: ConvWeight, bias, stride, act, residual=None):
@@ -324,7 +317,7 @@ class DeployPlan:
     def _bias_act(self, x, bias, act):
         B, C, H, W = x.shape
         assert x.is_contiguous(memory_format=torch.channels_last) and x.dtype == self.dtype
-        _lib.check(_lib.lib().fvit_bias_act_cl(self.code, x.data_ptr(), bias.data_ptr(), B * H * W, C, act, _stream(self.dev)),
+        _lib.check(_lib.lib().fvit_bias_act_cl(self.code, x.data_ptr(), bias.data_ptr(), B * H * W, C, act, _lib.stream_ptr(self.dev)),
                    "fvit_bias_act_cl")
         return x
 
@@ -332,7 +325,7 @@ class DeployPlan:
         B, C, H, W = x.shape
         assert x.is_contiguous(memory_format=torch.channels_last) and y.is_contiguous(memory_format=torch.channels_last)
         _lib.check(_lib.lib().fvit_bias_residual_cl(self.code, x.data_ptr(), y.data_ptr(), bias.data_ptr(), B * H * W, C,
-                                                    _stream(self.dev)), "fvit_bias_residual_cl")
+                                                    _lib.stream_ptr(self.dev)), "fvit_bias_residual_cl")
         return x
 
     def _pool_head(self, x, hw, hb):
@@ -342,7 +335,7 @@ class DeployPlan:
         B, C, H, W = x.shape
         if x.dtype in hat_runtime._DT and x.permute(0, 2, 3, 1).is_contiguous() and C % 16 == 0 and hw.shape[1] == C and hw.is_contiguous():
             feat = torch.empty((B, C), dtype=torch.float32, device=x.device)
-            _lib.check(_lib.lib().fvit_global_avgpool_cl(hat_runtime._DT[x.dtype], x.data_ptr(), feat.data_ptr(), B, H * W, C, _stream(self.dev)),
+            _lib.check(_lib.lib().fvit_global_avgpool_cl(hat_runtime._DT[x.dtype], x.data_ptr(), feat.data_ptr(), B, H * W, C, _lib.stream_ptr(self.dev)),
                        "fvit_global_avgpool_cl")
             return self._head_logits(feat, hw, hb)
         return F.linear(x.float().mean(dim=(2, 3)), hw, hb)
@@ -351,7 +344,7 @@ class DeployPlan:
         """The head on (B, C) fp32 pooled features: fvit_head_logits (exact-fp32 MFMA)."""
         B, C = feat.shape
         out = torch.empty((B, hw.shape[0]), dtype=torch.float32, device=feat.device)
-        _lib.check(_lib.lib().fvit_head_logits(feat.data_ptr(), hw.data_ptr(), hb.data_ptr(), out.data_ptr(), B, hw.shape[0], C, _stream(self.dev)),
+        _lib.check(_lib.lib().fvit_head_logits(feat.data_ptr(), hw.data_ptr(), hb.data_ptr(), out.data_ptr(), B, hw.shape[0], C, _lib.stream_ptr(self.dev)),
                    "fvit_head_logits")
         return out
 
@@ -365,7 +358,7 @@ class DeployPlan:
             return y.to(self.dtype).contiguous(memory_format=torch.channels_last)
         out = torch.empty_like(x)
         _lib.check(_lib.lib().fvit_layernorm2d_cl(self.code, x.data_ptr(), out.data_ptr(), w.data_ptr(), b.data_ptr(), eps,
-                                                  B * H * W, C, cv, _stream(self.dev)), "fvit_layernorm2d_cl")
+                                                  B * H * W, C, cv, _lib.stream_ptr(self.dev)), "fvit_layernorm2d_cl")
         return out
 
     # ---- forward -------------------------------------------------------------------------
@@ -492,7 +485,7 @@ class DeployPlan:
         lo = torch.empty_like(hi)
         _lib.check(_lib.lib().fvit_layernorm2d_px(self.code, x.data_ptr() if x is not None else None, x_lo.data_ptr() if x_lo is not None else None,
                                                   x_f32.data_ptr() if x_f32 is not None else None, hi.data_ptr(), lo.data_ptr(), w.data_ptr(),
-                                                  b.data_ptr(), eps, B * H * W, C, c_valid, _stream(self.dev)), "fvit_layernorm2d_px")
+                                                  b.data_ptr(), eps, B * H * W, C, c_valid, _lib.stream_ptr(self.dev)), "fvit_layernorm2d_px")
         return hi, lo
 
     # ---- the level walk ----------------------------------------------------------------------------------------------------
@@ -541,7 +534,7 @@ class DeployPlan:
                 B, _, Hi, Wi = x.shape
                 y = torch.empty((B, 64, (Hi - 1) // 2 + 1, (Wi - 1) // 2 + 1), dtype=self.dtype, device=x.device, memory_format=torch.channels_last)
                 view = hat_runtime._image_view(x)
-                args = (self.code, view, t["stem_k"].data_ptr(), t["stem_k_lo"].data_ptr(), st.bias0.data_ptr(), y.data_ptr(), B, Hi, Wi, _stream(self.dev))
+                args = (self.code, view, t["stem_k"].data_ptr(), t["stem_k_lo"].data_ptr(), st.bias0.data_ptr(), y.data_ptr(), B, Hi, Wi, _lib.stream_ptr(self.dev))
                 if u8:
                     _lib.check(_lib.lib().fvit_stem_conv3x3s2_px_u8(*args, norm), "fvit_stem_conv3x3s2_px_u8")
                 else:
@@ -554,7 +547,7 @@ class DeployPlan:
             y = torch.empty((B, 64, (H1 - 1) // 2 + 1, (W1 - 1) // 2 + 1), dtype=self.dtype, device=x.device,
                             memory_format=torch.channels_last)
             view = hat_runtime._image_view(x)
-            args = (self.code, view, t["stem_k"].data_ptr(), st.bias0.data_ptr(), wk1.data_ptr(), st.bias1.data_ptr(), y.data_ptr(), B, Hi, Wi, _stream(self.dev))
+            args = (self.code, view, t["stem_k"].data_ptr(), st.bias0.data_ptr(), wk1.data_ptr(), st.bias1.data_ptr(), y.data_ptr(), B, Hi, Wi, _lib.stream_ptr(self.dev))
             if u8:
                 _lib.check(_lib.lib().fvit_stem_fused_u8(*args, norm), "fvit_stem_fused_u8")
             else:
@@ -565,7 +558,7 @@ class DeployPlan:
             y = torch.empty((B, 64, (Hi - 1) // 2 + 1, (Wi - 1) // 2 + 1), dtype=self.dtype, device=x.device,
                             memory_format=torch.channels_last)
             view = hat_runtime._image_view(x)
-            args = (self.code, view, t["stem_k"].data_ptr(), st.bias0.data_ptr(), y.data_ptr(), B, Hi, Wi, _stream(self.dev))
+            args = (self.code, view, t["stem_k"].data_ptr(), st.bias0.data_ptr(), y.data_ptr(), B, Hi, Wi, _lib.stream_ptr(self.dev))
             if u8:
                 _lib.check(_lib.lib().fvit_stem_conv3x3s2_u8(*args, norm), "fvit_stem_conv3x3s2_u8")
             else:
@@ -754,7 +747,7 @@ class BackboneDeployPlan(DeployPlan):
         x = m.x
         if (Hp, Wp) != (H, W) and len(blocks):
             x = torch.empty((B, C, Hp, Wp), dtype=self.dtype, device=m.x.device, memory_format=torch.channels_last)
-            _lib.check(_lib.lib().fvit_map_pad_cl(self.code, m.x.data_ptr(), x.data_ptr(), B, H, W, Hp, Wp, C, _stream(self.dev)), "fvit_map_pad_cl")
+            _lib.check(_lib.lib().fvit_map_pad_cl(self.code, m.x.data_ptr(), x.data_ptr(), B, H, W, Hp, Wp, C, _lib.stream_ptr(self.dev)), "fvit_map_pad_cl")
         return LevelMap(self._conv_level(x, blocks)[0], H, W)
 
     def _hat_level_dyn(self, lvl, m: LevelMap, padded_out: bool) -> LevelMap:
@@ -771,7 +764,7 @@ class BackboneDeployPlan(DeployPlan):
         view = hat_runtime._map_view(m.x[:, :tw.channels, :m.H, :m.W])
         out = torch.empty((B, tw.channels, m.H, m.W), dtype=torch.float32, device=m.x.device)
         _lib.check(_lib.lib().fvit_feature_tap(ctypes.byref(view), B, tw.channels, m.H, m.W, tw.scale.data_ptr(), tw.shift.data_ptr(), out.data_ptr(),
-                                               _stream(self.dev)), "fvit_feature_tap")
+                                               _lib.stream_ptr(self.dev)), "fvit_feature_tap")
         return out
 
     def _downsample_crop(self, m: LevelMap, d: DownW) -> LevelMap:
@@ -782,7 +775,7 @@ class BackboneDeployPlan(DeployPlan):
             B, C, Hp, Wp = m.x.shape
             n = torch.empty((B, C, m.H, m.W), dtype=self.dtype, device=m.x.device, memory_format=torch.channels_last)
             _lib.check(_lib.lib().fvit_layernorm2d_crop_cl(self.code, m.x.data_ptr(), n.data_ptr(), d.ln_w.data_ptr(), d.ln_b.data_ptr(), d.eps,
-                                                           B, m.H, m.W, Hp, Wp, C, d.cin, _stream(self.dev)), "fvit_layernorm2d_crop_cl")
+                                                           B, m.H, m.W, Hp, Wp, C, d.cin, _lib.stream_ptr(self.dev)), "fvit_layernorm2d_crop_cl")
         y = self._conv(n, d.conv, None, 2, 0)
         return LevelMap(y, y.shape[2], y.shape[3])
 

@@ -46,14 +46,6 @@ def _dense32(t, align=4):
     return t.clone() if t.data_ptr() % align else t
 
 
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
-
-
 class _LabelMeta:
     """What one label launch needs besides the logits: per set the class map (int32 [R]) or dense targets ([R][C] fp32), (B, Q) and the scale."""
 
@@ -65,8 +57,8 @@ class _LabelMeta:
         sets = (_lib.FvitDetLabelSet * len(logits))()
         for s, lg in enumerate(logits):
             B, Q = self.shapes[s]
-            sets[s] = _lib.FvitDetLabelSet(logits=lg.data_ptr(), classes=_ptr(self.classes[s]), targets=_ptr(self.targets[s]),
-                                           grad_logits=_ptr(grads[s]) if grads is not None else None, R=B * Q, Q=Q, B=B, scale=self.scales[s])
+            sets[s] = _lib.FvitDetLabelSet(logits=lg.data_ptr(), classes=_lib.ptr(self.classes[s]), targets=_lib.ptr(self.targets[s]),
+                                           grad_logits=_lib.ptr(grads[s]) if grads is not None else None, R=B * Q, Q=Q, B=B, scale=self.scales[s])
         return sets
 
 
@@ -89,7 +81,7 @@ class _LabelLoss(torch.autograd.Function):
                 _lib.check(-1, "fvit_det_label_loss_workspace")
             ws = torch.empty(need, dtype=torch.uint8, device=dev)
             _lib.check(lib.fvit_det_label_loss(sets, n, meta.C, meta.alpha, meta.gamma, loss.data_ptr(), card.data_ptr(), stride, hits.data_ptr(),
-                                               ws.data_ptr(), need, _stream()), "fvit_det_label_loss")
+                                               ws.data_ptr(), need, _lib.stream_ptr()), "fvit_det_label_loss")
         ctx.meta, ctx.dtypes, ctx.shapes = meta, [lg.dtype for lg in logits], [lg.shape for lg in logits]
         ctx.save_for_backward(*wide)
         ctx.mark_non_differentiable(card, hits)
@@ -103,7 +95,7 @@ class _LabelLoss(torch.autograd.Function):
         flat = torch.empty(sum(w.numel() for w in wide), dtype=torch.float32, device=dev)      # the one (R, C) fp32 tensor per set
         grads = list(flat.split([w.numel() for w in wide]))
         with torch.cuda.device(dev):
-            _lib.check(_lib.lib().fvit_det_label_loss_backward(meta.table(wide, grads), n, meta.C, meta.alpha, meta.gamma, g.data_ptr(), _stream()),
+            _lib.check(_lib.lib().fvit_det_label_loss_backward(meta.table(wide, grads), n, meta.C, meta.alpha, meta.gamma, g.data_ptr(), _lib.stream_ptr()),
                        "fvit_det_label_loss_backward")
         out = [gr.view(sh).to(dt) if need else None for gr, sh, dt, need in zip(grads, ctx.shapes, ctx.dtypes, ctx.needs_input_grad[1:])]
         return (None, *out)
@@ -133,7 +125,7 @@ class _BoxLoss(torch.autograd.Function):
         out = torch.empty(n, 4, dtype=torch.float32, device=dev) if total else torch.zeros(n, 4, dtype=torch.float32, device=dev)
         if total:
             with torch.cuda.device(dev):
-                _lib.check(_lib.lib().fvit_det_box_loss(meta.table(wide), n, out.data_ptr(), _stream()), "fvit_det_box_loss")
+                _lib.check(_lib.lib().fvit_det_box_loss(meta.table(wide), n, out.data_ptr(), _lib.stream_ptr()), "fvit_det_box_loss")
         ctx.meta, ctx.dtypes = meta, [s.dtype for s in srcs]
         ctx.save_for_backward(*wide)
         return out
@@ -148,7 +140,7 @@ class _BoxLoss(torch.autograd.Function):
         grads = list(flat.split(rows))
         if sum(rows):
             with torch.cuda.device(dev):
-                _lib.check(_lib.lib().fvit_det_box_loss_backward(meta.table(wide, grads), n, g.data_ptr(), _stream()), "fvit_det_box_loss_backward")
+                _lib.check(_lib.lib().fvit_det_box_loss_backward(meta.table(wide, grads), n, g.data_ptr(), _lib.stream_ptr()), "fvit_det_box_loss_backward")
         return (None, *[gr.to(dt) if need else None for gr, dt, need in zip(grads, ctx.dtypes, ctx.needs_input_grad[1:])])
 
 

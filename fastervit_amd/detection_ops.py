@@ -56,10 +56,6 @@ def _float_input(who, name, t, grad_ok=True):
     return t.clone() if t.data_ptr() % 16 else t
 
 
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
 def _pairwise(who, mode, boxes1, boxes2):
     dt = boxes1.dtype if isinstance(boxes1, torch.Tensor) else None
     b1 = _float_input(who, "boxes1", boxes1, grad_ok=False)
@@ -71,7 +67,7 @@ def _pairwise(who, mode, boxes1, boxes2):
     union = torch.empty(N, M, dtype=torch.float32, device=b1.device) if mode == _lib.FVIT_BOX_IOU else None
     with torch.cuda.device(b1.device):
         _lib.check(_lib.lib().fvit_box_pairwise(mode, b1.data_ptr(), b2.data_ptr(), out.data_ptr(), union.data_ptr() if union is not None else None, N, M,
-                                                _stream()), "fvit_box_pairwise")
+                                                _lib.stream_ptr()), "fvit_box_pairwise")
     if dt != torch.float32:
         out = out.to(dt)
         union = union.to(dt) if union is not None else None
@@ -92,7 +88,7 @@ def _nms_launch(boxes, order, idxs, thr, keep, count, workspace, G, N):
     lib = _lib.lib()
     with torch.cuda.device(boxes.device):
         _lib.check(lib.fvit_box_nms(boxes.data_ptr(), order.data_ptr() if order is not None else None, idxs.data_ptr() if idxs is not None else None,
-                                    float(thr), keep.data_ptr(), count.data_ptr(), workspace.data_ptr(), workspace.numel(), G, N, _stream()), "fvit_box_nms")
+                                    float(thr), keep.data_ptr(), count.data_ptr(), workspace.data_ptr(), workspace.numel(), G, N, _lib.stream_ptr()), "fvit_box_nms")
 
 
 def nms_workspace(G: int, N: int, device) -> torch.Tensor:
@@ -173,7 +169,7 @@ def postprocess_launch(pred_logits, pred_boxes, target_sizes, scores, labels, bo
     lib = _lib.lib()
     with torch.cuda.device(pred_logits.device):
         _lib.check(lib.fvit_det_select(pred_logits.data_ptr(), pred_boxes.data_ptr(), target_sizes.data_ptr(), scores.data_ptr(), labels.data_ptr(),
-                                       query.data_ptr(), boxes.data_ptr(), B, Q, C, K, int(bool(not_to_xyxy)), int(bool(test)), _stream()), "fvit_det_select")
+                                       query.data_ptr(), boxes.data_ptr(), B, Q, C, K, int(bool(not_to_xyxy)), int(bool(test)), _lib.stream_ptr()), "fvit_det_select")
     if nms_iou_threshold > 0:
         if keep is None or count is None or workspace is None:
             raise RuntimeError(f"{who}: with NMS on, keep (B, K) int64, count (B,) int32 and workspace (nms_workspace(B, K, device)) are required")
@@ -264,7 +260,7 @@ class HungarianMatcher(nn.Module):
         with torch.cuda.device(logits.device):
             _lib.check(_lib.lib().fvit_det_matcher_cost(logits.data_ptr(), pred.data_ptr(), tgt_ids.data_ptr(), tgt.data_ptr(), cost.data_ptr(), R, C, T,
                                                         float(self.cost_class), float(self.cost_bbox), float(self.cost_giou), float(self.focal_alpha),
-                                                        _stream()), "fvit_det_matcher_cost")
+                                                        _lib.stream_ptr()), "fvit_det_matcher_cost")
         if dt != torch.float32:
             cost = cost.to(dt)
         return cost.view(bs, num_queries, T)

@@ -57,12 +57,6 @@ def _require_gpu(t: torch.Tensor, what: str) -> None:
             "there is no CPU or eager fallback. Move the model and input to the GPU.")
 
 
-def _stream_ptr(device=None) -> int:
-    """Raw hipStream_t of torch's current stream ON ``device`` (not on the thread's current device: a model moved with
-    ``.to('cuda:1')`` and called while cuda:0 is current must launch on a cuda:1 stream)."""
-    return torch.cuda.current_stream(device).cuda_stream
-
-
 def _check_device(x: torch.Tensor, layer, what: str) -> None:
     """The kernels dereference raw pointers: parameters and input must live on the same GPU."""
     for p in layer.parameters():
@@ -178,7 +172,7 @@ def normalize_u8(x: torch.Tensor, norm, mask: Optional[torch.Tensor] = None, out
         mask = mask.contiguous()
     with torch.cuda.device(x.device):
         _lib.check(_lib.lib().fvit_image_normalize_u8(_image_view(x), out.data_ptr(), 1 if cl else 0, B, C_, H, W, norm,
-                                                      mask.data_ptr() if mask is not None else None, _stream_ptr(x.device)), "fvit_image_normalize_u8")
+                                                      mask.data_ptr() if mask is not None else None, _lib.stream_ptr(x.device)), "fvit_image_normalize_u8")
     return out
 
 
@@ -663,7 +657,7 @@ def token_init(tok, xp: torch.Tensor) -> torch.Tensor:
         ct = torch.empty((B, Ho * Wo, Cc), dtype=torch.float32, device=xp.device)
         view = _map_view(xp)
         rc = _lib.lib().fvit_token_init(C.byref(view), w.data_ptr(), b.data_ptr(), ct.data_ptr(), B, Cc, Hp, Wp, kh, kw, sh, sw,
-                                        tok.window_size, _stream_ptr(xp.device))
+                                        tok.window_size, _lib.stream_ptr(xp.device))
         _lib.check(rc, "fvit_token_init")
         return ct
 
@@ -718,7 +712,7 @@ def token_init_dyn(tok, xp: torch.Tensor, ws: int) -> torch.Tensor:
         kh, kw, sh, sw, _, _, Hq, Wq = token_geometry(Hp, Wp, ws, cw)
         ct = torch.empty((B, Hq * Wq, Cc), dtype=torch.float32, device=xp.device)
         rc = _lib.lib().fvit_token_init_dyn(C.byref(_map_view(xp)), w.data_ptr(), b.data_ptr(), ct.data_ptr(), B, Cc, Hp, Wp, kh, kw, sh, sw,
-                                            cw, _stream_ptr(xp.device))
+                                            cw, _lib.stream_ptr(xp.device))
         _lib.check(rc, "fvit_token_init_dyn")
         return ct
 
@@ -761,7 +755,7 @@ def feature_tap(x: torch.Tensor, bn, H: Optional[int] = None, W: Optional[int] =
         scale, shift = _folded_bn(bn, x.device)
         out = torch.empty((B, Cc, H, W), dtype=torch.float32, device=x.device)
         rc = _lib.lib().fvit_feature_tap(C.byref(_map_view(x)), B, Cc, H, W, scale.data_ptr(), shift.data_ptr(), out.data_ptr(),
-                                         _stream_ptr(x.device))
+                                         _lib.stream_ptr(x.device))
         _lib.check(rc, "fvit_feature_tap")
         return out
 

@@ -27,10 +27,6 @@ import torch
 from . import _lib
 
 
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else t.data_ptr()
-
-
 def head_forward_backward(feat: torch.Tensor, target: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, grad_flat: torch.Tensor,
                           global_batch: int, smoothing: float, scratch: dict) -> None:
     """Kernel sequence of one local step: fills ``grad_flat`` = [dW | db | loss] (already divided by ``global_batch``)."""
@@ -56,7 +52,7 @@ def head_forward_backward(feat: torch.Tensor, target: torch.Tensor, weight: torc
     with torch.cuda.device(feat.device):
         st = torch.cuda.current_stream(feat.device).cuda_stream
         inv = C.c_float(1.0 / float(global_batch))
-        _lib.check(lib.fvit_head_logits(feat.data_ptr(), weight.data_ptr(), _ptr(bias), logits.data_ptr(), B, N, F, st), "fvit_head_logits")
+        _lib.check(lib.fvit_head_logits(feat.data_ptr(), weight.data_ptr(), _lib.ptr(bias), logits.data_ptr(), B, N, F, st), "fvit_head_logits")
         _lib.check(lib.fvit_head_softmax_xent(logits.data_ptr(), target.data_ptr(), loss_rows.data_ptr(), row_stats.data_ptr(), B, N,
                                               C.c_float(smoothing), inv, st), "fvit_head_softmax_xent")
         _lib.check(lib.fvit_head_grad(logits.data_ptr(), feat.data_ptr(), loss_rows.data_ptr(), grad_flat.data_ptr(), B, N, F, inv, st),

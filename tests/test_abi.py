@@ -58,6 +58,129 @@ def test_abi_version_and_struct_sizes(lib):
     assert ctypes.sizeof(_lib.FvitConvCall) == 11 * 8 + 4 + 8 * 4 + 4   # 4: tail padding to the pointers' alignment
 
 
+def _header():
+    return open(os.path.join(ROOT, "include", "fvit_hip.h")).read()
+
+
+def _edit(text, old, new):
+    assert text.count(old) == 1, old
+    return text.replace(old, new)
+
+
+def test_parser_reads_every_prototype():
+    """_lib.parse_header skips nothing: its names are those the independent regex of test_header_symbols_are_exported finds, section by section,
+    and EXPORTED_SYMBOLS / DIAG_SYMBOLS are those names."""
+    hdr = _header()
+    a, b = hdr.index("#ifdef FVIT_DIAG"), hdr.index("#endif /* FVIT_DIAG */")
+    product, diag = _lib.parse_header(hdr)
+    assert set(product) == set(re.findall(r"\b(fvit_[a-z0-9_]+)\s*\(", hdr[:a] + hdr[b:])) - {"fvit_stream_t"}
+    assert set(diag) == set(re.findall(r"\b(fvit_debug_[a-z0-9_]+)\s*\(", hdr[a:b])) and diag
+    assert _lib.EXPORTED_SYMBOLS == tuple(product) and _lib.DIAG_SYMBOLS == tuple(diag)
+    assert not any(s.startswith("fvit_debug_") for s in _lib.EXPORTED_SYMBOLS)
+
+
+def test_parser_spot_signatures():
+    """Six prototypes (and a size_t return, and the one override) against argtypes written out by hand from the header."""
+    vp, i32, i64, f32, sz, P = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t, ctypes.POINTER
+    product, _ = _lib.parse_header(_header())
+    assert product["fvit_ct_block_fused"] == (ctypes.c_int, [i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, f32,
+                                                             vp, vp, vp, vp, vp, vp, vp, f32, vp])
+    assert len(product["fvit_ct_block_fused"][1]) == 29
+    assert product["fvit_sgd_momentum"] == (ctypes.c_int, [vp, vp, vp, i64, f32, f32, f32, vp])
+    assert product["fvit_box_nms"] == (ctypes.c_int, [vp, vp, vp, f32, vp, vp, vp, sz, i32, i32, vp])
+    assert product["fvit_hat_stage_forward_tail"] == (ctypes.c_int, [
+        P(_lib.FvitStageDesc), P(_lib.FvitBlockWeights), P(_lib.FvitStageTables), P(_lib.FvitMapView), vp, P(_lib.FvitMapView),
+        P(_lib.FvitStageTail), vp, sz, vp])
+    assert product["fvit_bwd_blocks"] == (ctypes.c_int32, [i32])
+    assert product["fvit_last_error"] == (ctypes.c_char_p, [])
+    assert product["fvit_stage_workspace_bytes"] == (sz, [P(_lib.FvitStageDesc)])
+    assert product["fvit_tune"] == (ctypes.c_int, [ctypes.c_char_p, i32])
+    # the descriptor array of the resize kernel is DEVICE memory (callers pass data_ptr()): void* by _lib._ARG_OVERRIDES; the host query is typed
+    assert product["fvit_image_resize_u8"] == (ctypes.c_int, [vp, i32, P(_lib.FvitMapView), i32, i32, i32, vp, vp])
+    assert product["fvit_image_resize_check"] == (ctypes.c_int, [P(_lib.FvitResizeDesc), i32, i32])
+
+
+def test_parser_follows_header_edits():
+    """A changed prototype changes the parse: swapped parameter types, a dropped parameter, a type the binding has no rule for (an error that
+    names the function), a prototype moved into the FVIT_DIAG section."""
+    i64, f32, vp = ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
+    hdr = _header()
+    at = "int64_t n, float lr,"   # of fvit_sgd_momentum
+    assert _lib.parse_header(hdr)[0]["fvit_sgd_momentum"][1] == [vp, vp, vp, i64, f32, f32, f32, vp]
+    assert _lib.parse_header(_edit(hdr, at, "float n, int64_t lr,"))[0]["fvit_sgd_momentum"][1] == [vp, vp, vp, f32, i64, f32, f32, vp]
+    assert _lib.parse_header(_edit(hdr, at, "float lr,"))[0]["fvit_sgd_momentum"][1] == [vp, vp, vp, f32, f32, f32, vp]
+    for bad in ("long n, float lr,", "unsigned int n, float lr,", "int64_t n[2], float lr,", "float** n, float lr,", "FvitMapView n, float lr,"):
+        with pytest.raises(RuntimeError, match="fvit_sgd_momentum"):
+            _lib.parse_header(_edit(hdr, at, bad))
+    proto = "int fvit_tune(const char* key, int32_t value);"
+    product, diag = _lib.parse_header(_edit(_edit(hdr, proto, ""), "#endif /* FVIT_DIAG */", proto + "\n#endif /* FVIT_DIAG */"))
+    assert "fvit_tune" in diag and "fvit_tune" not in product
+    assert diag["fvit_tune"] == (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int32])
+
+
+def test_loaded_library_carries_the_header_signatures(lib):
+    """After _lib.lib() every product function of the handle has the header's restype and argtypes (the arity check ctypes then makes on every call)."""
+    product, _ = _lib.parse_header(_header())
+    for name, (restype, argtypes) in product.items():
+        fn = getattr(lib, name)
+        assert fn.restype == restype and list(fn.argtypes) == argtypes and len(fn.argtypes) == len(argtypes), name
+
+
+def _header_structs(text):
+    """{name: [(field, C type)]} of every `typedef struct ... Name;` of the header, `int32_t H, W;` as two fields, `char tag[24]` as type char[24]."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    out = {}
+    for body, name in re.findall(r"typedef\s+struct\s*\w*\s*\{([^{}]*)\}\s*(\w+)\s*;", text):
+        fields = []
+        for decl in filter(None, (d.strip() for d in body.split(";"))):
+            first, *more = [d.strip() for d in decl.split(",")]
+            m = re.fullmatch(r"(.*?)(\w+)\s*(\[\d+\])?", first, re.S)
+            assert m and all(re.fullmatch(r"\w+", n) for n in more), f"{name}: {decl}"
+            ctype = " ".join(m.group(1).split()) + (m.group(3) or "")
+            fields += [(n, ctype) for n in [m.group(2)] + more]
+        out[name] = fields
+    return out
+
+
+def _field_ctype(ctype, where):
+    m = re.fullmatch(r"char\[(\d+)\]", ctype)
+    if m:
+        return ctypes.c_char * int(m.group(1))
+    nested = getattr(_lib, ctype, None)
+    if isinstance(nested, type) and issubclass(nested, ctypes.Structure):
+        return nested
+    return _lib.ctype_of(ctype, where)[0]
+
+
+def test_structs_mirror_the_header_field_by_field():
+    """Every struct of the header (product and diagnosis sections) is a _lib class with the same fields in the same order and of the same types
+    (the type rule of the prototypes, plus char[N] and nested structs; `in_` stands for `in`); _lib has no struct the header lacks."""
+    structs = _header_structs(_header())
+    assert len(structs) >= 15 and structs["FvitStageDesc"][5:7] == [("H", "int32_t"), ("W", "int32_t")]
+    assert structs["FvitDebugRowhashRecord"][0] == ("tag", "char[24]")
+    for name, fields in structs.items():
+        cls = getattr(_lib, name, None)
+        assert isinstance(cls, type) and issubclass(cls, ctypes.Structure), f"_lib has no struct {name}"
+        want = [(n, _field_ctype(t, f"{name}.{n}")) for n, t in fields]
+        got = [(n[:-1] if n.endswith("_") else n, t) for n, t in cls._fields_]
+        assert got == want, name
+    mine = {n for n, v in vars(_lib).items() if isinstance(v, type) and issubclass(v, ctypes.Structure) and v.__module__ == _lib.__name__}
+    assert mine == set(structs)
+
+
+def test_constants_match_the_header():
+    """Every FVIT_* number of _lib is a #define of the header with the same value."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", _header(), flags=re.S)
+    defines = {n: (float(v.rstrip("f")) if "." in v else int(v))
+               for n, v in re.findall(r"^[ \t]*#define[ \t]+(FVIT_\w+)[ \t]+\(?(-?[0-9][0-9.]*f?)\)?[ \t]*$", text, re.M)}
+    assert len(defines) >= 35 and defines["FVIT_EINVAL"] == -1 and defines["FVIT_MASK_BIAS"] == -30000.0
+    carried = {n: v for n, v in vars(_lib).items() if n.startswith("FVIT_") and isinstance(v, (int, float)) and not isinstance(v, bool)}
+    assert len(carried) >= 15 and "FVIT_ABI_VERSION" in carried
+    for n, v in carried.items():
+        assert n in defines, f"_lib.{n} is not a #define of the header"
+        assert v == defines[n] and type(v) is type(defines[n]), n
+
+
 def test_attention_spad(lib):
     for S, want in [(16, 16), (36, 48), (49, 64), (53, 64), (60, 64), (148, 160), (196, 208), (129, 160)]:
         assert lib.fvit_attention_spad(S) == want
