@@ -600,7 +600,7 @@ struct HaloParams {
     void* out;           // [M][64]
     const void* zeros;
     int B, H, W, act;
-    int tiles_x, tiles_y, tiles;
+    int tiles_x, tiles_y, strips, tiles;   // edge_tiling(H, W): per image tiles_x * tiles_y plain tiles, then `strips` strip tiles
     int buf_bytes;       // LDS bytes per tile buffer: HALO_BYTES (+ HALO_RES_BYTES with a residual)
     int ablate;          // experiment knob (results are wrong when non-zero): 1 no MFMA loop, 2 no halo/residual DMA, 4 no stores, 8 no epilogue math
     const float* ln_w;   // LN instance only (fvit_conv3x3_c64_ln2d): LayerNorm2d weight / bias [64] applied to the stored map
@@ -615,6 +615,28 @@ constexpr int HALO_RES_BYTES = HALO_TH * HALO_TW * 128;         // the tile's re
 constexpr int HALO_BUF = HALO_BYTES + HALO_RES_BYTES;
 
 constexpr int HALO_LN_LDS = 1024 + 2 * HALO_BUF + 1024;        // LN instance: 81 920 B, exactly half a CU's LDS (two workgroups per CU)
+
+// Tiling of an H x W map by conv3x3_c64_halo_kernel and stem_fused_kernel (there: of the final map).  Plain tiles are 8 rows x 16 columns.  When the last
+// tile column would hold Wr = W mod 16 <= 8 real columns, those columns are instead tiled by a STRIP of transposed tiles, 16 rows x 8 columns: the same
+// 10 x 18 halo image and the same MFMA loop with the roles of x and y swapped, half as many tiles for the strip.  Taken only where it lowers the tile count
+// (H > 8) and fvit_tune "conv_edge_tiles" (default 1) allows; 56 x 56: 21 + 4 = 25 tiles per image instead of 28.
+// Tiles are numbered per image: tiles_x * tiles_y plain tiles (x fastest), then `strips` strip tiles from the top.
+struct EdgeTiling { int tiles_x, tiles_y, strips; };
+inline EdgeTiling edge_tiling(int H, int W, int edge_tiles) {
+    EdgeTiling t{(W + HALO_TW - 1) / HALO_TW, (H + HALO_TH - 1) / HALO_TH, 0};
+    const int wr = W % HALO_TW, strips = (H + HALO_TW - 1) / HALO_TW;
+    if (edge_tiles && wr >= 1 && wr <= HALO_TH && strips < t.tiles_y) { t.tiles_x = W / HALO_TW; t.strips = strips; }
+    return t;
+}
+// tile -> image, origin of the tile in the map, and its kind (tr: a strip tile: tile pixel (row, s) is map pixel (y0 + s, x0 + row)); wave-uniform
+struct TilePos { int b, y0, x0; bool tr; };
+__device__ inline TilePos tile_pos(int tile, int tiles_x, int tiles_y, int strips) {
+    const int plain = tiles_x * tiles_y, per_img = plain + strips;
+    const int b = tile / per_img, t = tile - b * per_img;
+    if (t >= plain) return TilePos{b, (t - plain) * HALO_TW, tiles_x * HALO_TW, true};
+    const int ty = t / tiles_x;
+    return TilePos{b, ty * HALO_TH, (t - ty * tiles_x) * HALO_TW, false};
+}
 
 // LN (the conv that ends a level: bias + residual epilogue only): the stored map is LayerNorm2d, over the 64 channels of a pixel, of the map the plain
 // instance stores -- statistics in fp32 from the ROUNDED 16-bit values, two passes (mean, then squared deviations), each reduced in-lane (8 channels),
@@ -675,11 +697,12 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_halo_kernel(HaloParams p) 
     // residual read offset: pixel (row, s) of the tile at (row*16 + s)*128, chunk c at position c ^ ((s >> 1) & 7)
     const int roff = HALO_BYTES + (ph * 4 * HALO_TW + s) * 128 + (((ch * 4 + g) ^ ((s >> 1) & 7)) << 4);
 
+    // a strip tile (tr) holds the transposed halo: LDS pixel (hy, hx) is map pixel (y0 + hx, x0 + hy), and likewise its residual pixels
     auto stage = [&](int tile, char* buf) {
-        const int tx = tile % p.tiles_x, t2 = tile / p.tiles_x;
-        const int ty = t2 % p.tiles_y, b = t2 / p.tiles_y;
-        const int y0 = ty * HALO_TH - 1, x0 = tx * HALO_TW - 1;
-        const size_t ib = (size_t)b * p.H * p.W * 64;
+        const TilePos tp = tile_pos(tile, p.tiles_x, p.tiles_y, p.strips);
+        const bool tr = tp.tr;
+        const int y0 = tp.y0 - 1, x0 = tp.x0 - 1;
+        const size_t ib = (size_t)tp.b * p.H * p.W * 64;
         // the halo coordinates are tile independent, but keeping 6 x (hy, hx, chunk) live across the MFMA loop costs
         // more registers than the weights leave: recompute them per tile (a handful of VALU ops per 1-KiB piece)
         int lane8 = lane >> 3;
@@ -690,7 +713,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_halo_kernel(HaloParams p) 
             if (piece < HALO_PIECES) {
                 const int hp = piece * 8 + lane8;
                 const int hy = hp / HALO_PW, hx = hp - hy * HALO_PW;
-                const int y = y0 + hy, x = x0 + hx;
+                const int y = y0 + (tr ? hx : hy), x = x0 + (tr ? hy : hx);
                 const bool ok = hy < HALO_PH && y >= 0 && y < p.H && x >= 0 && x < p.W;
                 const int c = (lane & 7) ^ (hx & 6);
                 const T* src = ok ? In + ib + ((size_t)y * p.W + x) * 64 + c * 8 : Z + c * 8;
@@ -702,7 +725,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_halo_kernel(HaloParams p) 
             for (int i = 0; i < 4; ++i) {
                 const int piece = wave * 4 + i;            // 8 pixels of tile row piece >> 1
                 const int col = (piece & 1) * 8 + lane8;
-                const int y = y0 + 1 + (piece >> 1), x = x0 + 1 + col;
+                const int y = y0 + 1 + (tr ? col : piece >> 1), x = x0 + 1 + (tr ? piece >> 1 : col);
                 const bool ok = y < p.H && x < p.W;
                 const int c = (lane & 7) ^ ((col >> 1) & 7);
                 const T* src = ok ? R + ib + ((size_t)y * p.W + x) * 64 + c * 8 : Z + c * 8;
@@ -717,14 +740,15 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_halo_kernel(HaloParams p) 
     v8 pk[4];
     int ptile = -1;
     auto flush = [&](int tile) {
-        const int tx = tile % p.tiles_x, t2 = tile / p.tiles_x;
-        const int ty = t2 % p.tiles_y, b = t2 / p.tiles_y;
-        const int x = tx * HALO_TW + s;
+        // tile pixel (4ph + mi, s): one address per lane and a wave-uniform step per mi -- a map row, or in a strip tile one pixel
+        const TilePos tp = tile_pos(tile, p.tiles_x, p.tiles_y, p.strips);
+        const int y = tp.y0 + (tp.tr ? s : ph * 4), x = tp.x0 + (tp.tr ? ph * 4 : s);
+        const int dy = tp.tr ? 0 : 1, dx = tp.tr ? 1 : 0;
+        T* o = O + (((size_t)tp.b * p.H + y) * p.W + x) * 64 + nb;
+        const int step = (tp.tr ? 1 : p.W) * 64;
 #pragma unroll
-        for (int mi = 0; mi < 4; ++mi) {
-            const int y = ty * HALO_TH + ph * 4 + mi;
-            if (y < p.H && x < p.W) *(v8*)(O + (((size_t)b * p.H + y) * p.W + x) * 64 + nb) = pk[mi];
-        }
+        for (int mi = 0; mi < 4; ++mi)
+            if (y + mi * dy < p.H && x + mi * dx < p.W) *(v8*)(o + mi * step) = pk[mi];
     };
 
     int tile = t_begin + idx;
@@ -746,6 +770,19 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_halo_kernel(HaloParams p) 
         // 18 groups (tap, K half) of 4 B-fragment reads + 8 MFMAs, software pipelined by hand one group ahead; the
         // scheduling barriers keep the compiler from hoisting more reads than that (it otherwise runs out of registers
         // next to the 144 weight VGPRs and spills the read offsets, whose reload would queue behind the LDS-DMA)
+        // A strip tile walks the same taps (ky, kx) of the map in the same order with the same weights -- the same sums in the same order -- and reads tap
+        // (ky, kx) from its transposed halo at row shift kx, column offset xoff[ky].  Tap (ky, kx) is at hb + ko[0][ky] + ko[1][kx] for both kinds: the kind
+        // (wave-uniform) picks the six offsets once per tile, the loop is the same code.  A row shift is a multiple of 256: it leaves bit 6 to the K half.
+        static_assert((HALO_PW * 128) % 256 == 0, "a row shift must leave bit 6 of a read offset alone");
+        int ko[2][3];
+        {
+            const bool tr = tile_pos(tile, p.tiles_x, p.tiles_y, p.strips).tr;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                ko[0][k] = tr ? xoff[k] : k * (HALO_PW * 128);
+                ko[1][k] = tr ? k * (HALO_PW * 128) : xoff[k];
+            }
+        }
         v8 xf[2][4];
 #pragma unroll
         for (int mi = 0; mi < 4; ++mi) xf[0][mi] = *(const v8*)(hb + mi * (HALO_PW * 128) + xoff[0]);
@@ -756,9 +793,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_halo_kernel(HaloParams p) 
             const int tap = q >> 1, kk = q & 1;
             if (q + 1 < 18) {
                 const int tap1 = (q + 1) >> 1, kk1 = (q + 1) & 1, ky1 = tap1 / 3, kx1 = tap1 - ky1 * 3;
-                const int o = xoff[kx1] ^ (kk1 << 6);
+                const int o = (ko[0][ky1] + ko[1][kx1]) ^ (kk1 << 6);
 #pragma unroll
-                for (int mi = 0; mi < 4; ++mi) xf[(q + 1) & 1][mi] = *(const v8*)(hb + (mi + ky1) * (HALO_PW * 128) + o);
+                for (int mi = 0; mi < 4; ++mi) xf[(q + 1) & 1][mi] = *(const v8*)(hb + mi * (HALO_PW * 128) + o);
             }
 #pragma unroll
             for (int ni = 0; ni < 2; ++ni)
@@ -767,7 +804,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c64_halo_kernel(HaloParams p) 
             __builtin_amdgcn_sched_barrier(0);
         }
 
-        // ---- epilogue math: lane holds out[b][y][x][nb .. nb+7] for rows y = 8ty + 4ph + mi, column x = 16tx + s ----
+        // ---- epilogue math: lane holds channels nb .. nb+7 of tile pixels (row 4ph + mi, s): out[b][y0 + row][x0 + s], strip tile out[b][y0 + s][x0 + row] ----
         float bias[8];
         {
             const f4 t0 = *(const f4*)(sbias + nb), t1 = *(const f4*)(sbias + nb + 4);
@@ -1177,7 +1214,7 @@ struct StemFusedParams {
     const float* b2;     // [64]
     void* out;           // [B][H2][W2][64]
     int B, Hi, Wi, H1, W1, H2, W2;
-    int tiles_x, tiles_y, tiles;
+    int tiles_x, tiles_y, strips, tiles;   // edge_tiling(H2, W2)
     unsigned long long* ts;   // TS instance only (fvit_debug_stem_timeline): per wave [workgroup][wave][8] accumulated s_memtime ticks:
                               // 0 phase A (gathers + conv1 + LDS writes), 1 barrier after A, 2 phase B, 3 epilogue, 4 barrier before A, 5 tiles, 6 total
     float nscale[3], nshift[3];   // IN = uint8_t: every gathered byte u of channel c becomes fmaf(u, nscale[c], nshift[c]) (fvit_stem_fused_u8)
@@ -1267,9 +1304,12 @@ __global__ __launch_bounds__(256, 2) void stem_fused_kernel(StemFusedParams p) {
     }
 
     for (int tile = t_begin + idx; tile < t_end; tile += per_xcd) {
-        const int tx = tile % p.tiles_x, t2 = tile / p.tiles_x;
-        const int ty = t2 % p.tiles_y, b = t2 / p.tiles_y;
-        const int r0 = 2 * ty * HALO_TH - 1, c0 = 2 * tx * HALO_TW - 1;      // conv1 coordinates of local (0, 0)
+        // a strip tile (tr, edge_tiling) holds the transposed conv1 image: the 33 LDS columns with their even / odd planes run along conv1 y, the 17 LDS
+        // rows along conv1 x -- LDS pixel (lr, lc) is conv1 pixel (r0 + lc, c0 + lr); its gather and k slots are those of any conv1 pixel
+        const TilePos tp = tile_pos(tile, p.tiles_x, p.tiles_y, p.strips);
+        const bool tr = tp.tr;
+        const int b = tp.b;
+        const int r0 = 2 * tp.y0 - 1, c0 = 2 * tp.x0 - 1;      // conv1 coordinates of local (0, 0)
         if constexpr (TS) { tsMark = __builtin_amdgcn_s_memtime(); tsN += 1; }
         __syncthreads();   // every wave is done reading the previous tile's conv1 image (and sb1 / sb2 are visible)
         FVIT_SF_MARK(tsBar0)
@@ -1299,7 +1339,7 @@ __global__ __launch_bounds__(256, 2) void stem_fused_kernel(StemFusedParams p) {
                 for (int u = 0; u < SF_BATCH; ++u) {
                     const int q = (g3 + 4 * u) * 16 + lane_s;
                     const int lr = q / SF_COLS, lc = q - lr * SF_COLS;
-                    const int R = r0 + lr, Cc = c0 + lc;
+                    const int R = r0 + (tr ? lc : lr), Cc = c0 + (tr ? lr : lc);
                     const bool v1 = q < SF_ROWS * SF_COLS && R >= 0 && R < p.H1 && Cc >= 0 && Cc < p.W1;
                     const int yi = 2 * R - 1, xi = 2 * Cc - 1;
                     qv[u] = q; lrv[u] = lr; lcv[u] = lc; v1v[u] = v1;
@@ -1424,10 +1464,9 @@ __global__ __launch_bounds__(256, 2) void stem_fused_kernel(StemFusedParams p) {
             unsigned pf0 = 0, pf1 = 0;
             const bool do_pf = false && esz == 4 && sw == esz && tile + per_xcd < t_end;   // measured r03: no gain (the gathers are instruction-bound, not miss-bound): off
             if (do_pf) {
-                const int nt = tile + per_xcd;
-                const int ntx = nt % p.tiles_x, nt2 = nt / p.tiles_x;
-                const int nty = nt2 % p.tiles_y, nbi = nt2 / p.tiles_y;
-                const int y0 = 4 * nty * HALO_TH - 3, x0 = 4 * ntx * HALO_TW - 3;     // 2 * (2 ty TH - 1) - 1
+                const TilePos np = tile_pos(tile + per_xcd, p.tiles_x, p.tiles_y, p.strips);   // (a strip tile's patch is 67 rows x 35 columns: not probed as such)
+                const int nbi = np.b;
+                const int y0 = 4 * np.y0 - 3, x0 = 4 * np.x0 - 3;     // 2 * (2 y0 - 1) - 1
                 const unsigned* nib = (const unsigned*)((const char*)p.in.data + (int64_t)nbi * p.in.stride_b * 4);
                 const int it0 = tid, it1 = tid + 256;                                  // 105 (row, plane) pairs x 4 column probes = 420 items
                 const int rc0 = it0 >> 2, rc1 = it1 >> 2;
@@ -1445,7 +1484,7 @@ __global__ __launch_bounds__(256, 2) void stem_fused_kernel(StemFusedParams p) {
                 for (int u = 0; u < SF_BATCH; ++u) {
                     const int q = (g3 + 4 * u) * 16 + lane_s;
                     const int lr = q / SF_COLS, lc = q - lr * SF_COLS;
-                    const int R = r0 + lr, Cc = c0 + lc;
+                    const int R = r0 + (tr ? lc : lr), Cc = c0 + (tr ? lr : lc);
                     const bool v1 = q < SF_ROWS * SF_COLS && R >= 0 && R < p.H1 && Cc >= 0 && Cc < p.W1;
                     const int yi = 2 * R - 1, xi = 2 * Cc - 1;
                     qv[u] = q; lrv[u] = lr; lcv[u] = lc; v1v[u] = v1;
@@ -1508,14 +1547,22 @@ __global__ __launch_bounds__(256, 2) void stem_fused_kernel(StemFusedParams p) {
 #pragma unroll
         for (int mi = 0; mi < 4; ++mi) xf[0][mi] = *(const v8*)(hb + (2 * mi) * SF_ROWPITCH + xoff[0]);
         __builtin_amdgcn_sched_barrier(0);
+        // as in conv3x3_c64_halo_kernel: tap (ky, kx) is at hb + ko[0][ky] + ko[1][kx]; a strip tile reads it at row shift kx, column offset xoff[ky]
+        static_assert(SF_ROWPITCH % 256 == 0, "a row shift must leave bit 6 of a read offset alone");
+        int ko[2][3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            ko[0][k] = tr ? xoff[k] : k * SF_ROWPITCH;
+            ko[1][k] = tr ? k * SF_ROWPITCH : xoff[k];
+        }
 #pragma unroll
         for (int q = 0; q < 18; ++q) {
             const int tap = q >> 1, kk = q & 1;
             if (q + 1 < 18) {
                 const int tap1 = (q + 1) >> 1, kk1 = (q + 1) & 1, ky1 = tap1 / 3, kx1 = tap1 - ky1 * 3;
-                const int o = xoff[kx1] ^ (kk1 << 6);
+                const int o = (ko[0][ky1] + ko[1][kx1]) ^ (kk1 << 6);
 #pragma unroll
-                for (int mi = 0; mi < 4; ++mi) xf[(q + 1) & 1][mi] = *(const v8*)(hb + (2 * mi + ky1) * SF_ROWPITCH + o);
+                for (int mi = 0; mi < 4; ++mi) xf[(q + 1) & 1][mi] = *(const v8*)(hb + (2 * mi) * SF_ROWPITCH + o);
             }
 #pragma unroll
             for (int ni = 0; ni < 2; ++ni)
@@ -1525,13 +1572,13 @@ __global__ __launch_bounds__(256, 2) void stem_fused_kernel(StemFusedParams p) {
         }
 
         FVIT_SF_MARK(tsB)
-        // ---- epilogue: bias + ReLU, out[b][y][x][nb .. nb+7] for rows y = 8ty + 4ph + mi, column x = 16tx + s ----
+        // ---- epilogue: bias + ReLU of tile pixels (row 4ph + mi, s): out[b][y0 + row][x0 + s][nb .. nb+7], strip tile out[b][y0 + s][x0 + row] ----
         const f4 t0 = *(const f4*)(sb2 + nb), t1 = *(const f4*)(sb2 + nb + 4);
         const float bias[8] = {t0[0], t0[1], t0[2], t0[3], t1[0], t1[1], t1[2], t1[3]};
-        const int x = tx * HALO_TW + s;
 #pragma unroll
         for (int mi = 0; mi < 4; ++mi) {
-            const int y = ty * HALO_TH + ph * 4 + mi;
+            const int row = ph * 4 + mi;
+            const int y = tp.y0 + (tr ? s : row), x = tp.x0 + (tr ? row : s);
             if (y < p.H2 && x < p.W2) {
                 v8 ov;
 #pragma unroll
@@ -1696,12 +1743,20 @@ int run_conv(ConvRoute r, const FvitConvCall& c, const FvitConvWeights& w, hipSt
         p.ln_w = ln ? c.ln_w : nullptr; p.ln_b = c.ln_b; p.ln_eps = c.ln_eps;
         p.in = c.in; p.w = w.classic; p.bias = c.bias; p.res = c.residual; p.out = c.out; p.zeros = c.zeros;
         p.B = c.B; p.H = c.Hi; p.W = c.Wi; p.act = c.act;
-        p.tiles_x = (c.Wi + HALO_TW - 1) / HALO_TW; p.tiles_y = (c.Hi + HALO_TH - 1) / HALO_TH;
-        p.tiles = c.B * p.tiles_x * p.tiles_y;   // <= M, which fits int32
+        // Not a route: how the kernel tiles the map.  Not with GELU: a strip tile computes a pixel in another of the epilogue's four unrolled row copies, and
+        // hipcc contracts gelu_fast's last step, hx * (z q) + hx with hx = 0.5 x, differently from copy to copy (fma(hx, z q, hx) or fma(0.5, x, hx * (z q)):
+        // both are allowed), so a GELU map's bits depend on the pixel's row in its tile -- the bias / ReLU / residual / LayerNorm2d epilogues have no such choice
+        const EdgeTiling et = edge_tiling(c.Hi, c.Wi, c.act != 2 && tune_get("conv_edge_tiles", 1));
+        p.tiles_x = et.tiles_x; p.tiles_y = et.tiles_y; p.strips = et.strips;
+        p.tiles = c.B * (p.tiles_x * p.tiles_y + p.strips);   // <= M, which fits int32
         p.ablate = diag_knob("conv_halo_ablate");
         int maxgrid = tune_get("conv_halo_grid", 512);   // 2 workgroups per CU (230 VGPRs, 46 KiB LDS each)
         if (maxgrid < 8) maxgrid = 8;                    // every XCD's tile range needs at least one workgroup
-        const int grid = p.tiles < maxgrid ? p.tiles : maxgrid;
+        // the launch shape is the plain tiling's, with or without the strip (launch records and roofline rows key on kernel name x workgroups): below the cap a
+        // strip leaves a few workgroups with an empty tile range
+        const EdgeTiling pt = edge_tiling(c.Hi, c.Wi, 0);
+        const int plain_tiles = c.B * pt.tiles_x * pt.tiles_y;
+        const int grid = plain_tiles < maxgrid ? plain_tiles : maxgrid;
         ProfScope prof(FVIT_K_CONV, 2.0 * M * 64.0 * 576.0, 2.0 * ((double)M * 64 * (c.residual ? 3.0 : 2.0) + 576.0 * 64), stream);
         prof_note(name, grid);
         p.buf_bytes = c.residual ? HALO_BUF : HALO_BYTES;
@@ -2011,9 +2066,9 @@ static int stem_fused_impl(int32_t dtype, const FvitMapView* in, const void* w1,
     p.in = *in; p.w1 = w1; p.b1 = b1; p.w2 = w2; p.b2 = b2; p.out = out; p.B = B; p.Hi = Hi; p.Wi = Wi;
     p.H1 = (Hi - 1) / 2 + 1; p.W1 = (Wi - 1) / 2 + 1;
     p.H2 = (p.H1 - 1) / 2 + 1; p.W2 = (p.W1 - 1) / 2 + 1;
-    p.tiles_x = (p.W2 + HALO_TW - 1) / HALO_TW;
-    p.tiles_y = (p.H2 + HALO_TH - 1) / HALO_TH;
-    const int64_t tiles = (int64_t)B * p.tiles_x * p.tiles_y;
+    const fvit::EdgeTiling et = fvit::edge_tiling(p.H2, p.W2, tune_get("conv_edge_tiles", 1));
+    p.tiles_x = et.tiles_x; p.tiles_y = et.tiles_y; p.strips = et.strips;
+    const int64_t tiles = (int64_t)B * ((int64_t)p.tiles_x * p.tiles_y + p.strips);
     if (tiles > 0x7fffffff || (int64_t)B * p.H2 * p.W2 > 0x7fffffff) {
         set_error("stem_fused: too many output pixels");
         return FVIT_EINVAL;
@@ -2023,7 +2078,10 @@ static int stem_fused_impl(int32_t dtype, const FvitMapView* in, const void* w1,
     for (int c = 0; c < 3; ++c) { p.nscale[c] = u8 ? norm[c] : 1.f; p.nshift[c] = u8 ? norm[3 + c] : 0.f; }
     int maxgrid = tune_get("stem_fused_grid", 512);
     if (maxgrid < 8) maxgrid = 8;
-    const int grid = p.tiles < maxgrid ? p.tiles : maxgrid;
+    // the launch shape is the plain tiling's (as in run_conv's halo launch): below the cap a strip leaves a few workgroups with an empty tile range
+    const fvit::EdgeTiling pt = fvit::edge_tiling(p.H2, p.W2, 0);
+    const int64_t plain_tiles = (int64_t)B * pt.tiles_x * pt.tiles_y;   // >= tiles, <= the pixel count checked above
+    const int grid = plain_tiles < maxgrid ? (int)plain_tiles : maxgrid;
     // fp32 channels-last image (stride_c 1, stride_w 3, rows and images dword-addressable from the image base with 32-bit offsets): the contiguous-run gather
     // uint8 channels-last (the decoder's HWC): the same gather on nine contiguous bytes (at least two columns: a run never spans more than the row's neighbours)
     const bool nhwc3 = (in->dtype == FVIT_F32 || (u8 && Wi >= 2)) && in->stride_c == 1 && in->stride_w == 3 && in->stride_h == 3 * (int64_t)Wi &&

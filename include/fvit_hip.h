@@ -847,6 +847,8 @@ int fvit_det_box_loss_backward(const FvitDetBoxSet* sets, int32_t n_sets, const 
  *   local rows, as the tables of every caller here do);
  *   "stage_exit_fused" 1/0: with a LayerNorm2d tail the last 4-wave C = 256 MLP kernel writes the normalised 16-bit map in place of the window_reverse +
  *   LayerNorm2d pass (same rounded values, another summation order of the statistics).
+ *   "conv_edge_tiles" 1/0: the 64-channel halo conv (without GELU) and the fused stem tile the last, at most half full 8 x 16 tile column of their map as a strip of
+ *   transposed 16 x 8 tiles (bitwise the same result).
  *   Removed in r06 with the kernel instances they selected (all measured no better than the defaults): "gemm_ring", "gemm_3stage_max_grid", "mlp_ring4_max_grid",
  *   "win_mlp256_depth", "win_stage3", "win_mlp256" = 1 / 3, "mlp_variant" = 2 / 4 / 5 / 6.
  * Guarded by a mutex; launches read the values at launch time.
