@@ -95,6 +95,10 @@ class FvitDetBoxSet(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("src", "tgt", "grad_src")] + [("M", C.c_int32), ("scale", C.c_float)]
 
 
+class FvitDetAssignSet(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("cost", "src", "tgt")] + [(n, C.c_int32) for n in ("Q", "T", "n_pairs", "_pad")]
+
+
 class FvitConvWeights(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("classic", "dense", "band_frag")] + [("terms", C.c_int32), ("cin_valid", C.c_int32)]
 

@@ -10,8 +10,10 @@ Drop-ins, by signature, key set and value, for the reference's ``models/dino/uti
 ``SetCriterion.forward`` collects every output set of the step (main, aux, interm, enc and the denoising sets) first and then runs all label losses in
 ceil(sets / 16) calls of the label kernel and all box losses in as many of the box kernel, each call one ``autograd.Function``.  With this library's
 ``HungarianMatcher`` (anything that has ``cost_matrix``) all sets are matched behind ONE device -> host copy of the concatenated cost matrices; any other
-matcher is called per set, as the reference does.  The one-hot target tensor is never built: the kernel takes a per-row class map, which is formed for
-all sets at once from one host -> device copy of the matched indices.  The denoising indices are host tensors.
+matcher is called per set, as the reference does.  With ``HungarianMatcher(solver="device")`` the assignment is solved on the device (DESIGN.md section
+17): ``forward`` then copies nothing to the host and never waits for the device, and ``return_indices`` gives device tensors.  The one-hot target
+tensor is never built: the kernel takes a per-row class map, which is formed for all sets at once from one host -> device copy of the matched indices
+(of the offsets the solver's indices are added to, on the device path).  The denoising indices are host tensors.
 
 16-bit inputs are widened to fp32 once and gradients come back in the input dtype; float64 is refused by name; a CPU tensor raises (there is no CPU or
 eager fallback).  ``'masks'`` raises NotImplementedError: segmentation is not part of this library.
@@ -172,8 +174,9 @@ def _host_indices(indices):
 class _Job:
     """One output set of the step: its outputs dict, indices, num_boxes and the suffix of its keys."""
 
-    def __init__(self, suffix, outputs, indices, num_boxes, log):
+    def __init__(self, suffix, outputs, indices, num_boxes, log, pairs=None):
         self.suffix, self.outputs, self.indices, self.num_boxes, self.log = suffix, outputs, indices, float(num_boxes), log
+        self.pairs = pairs      # the device solver's (2, P) int64 tensor behind ``indices``: the host then knows only where its pairs go
 
 
 class SetCriterion(nn.Module):
@@ -213,17 +216,29 @@ class SetCriterion(nn.Module):
             ref = job.outputs["pred_logits"] if "pred_logits" in job.outputs else job.outputs["pred_boxes"]
             B, Q = ref.shape[:2]
             assert B == len(targets), f"{who}: {B} images in the outputs, {len(targets)} target dicts"
-            idx = _host_indices(job.indices)
-            rows.append(np.concatenate([b * Q + i for b, (i, _) in enumerate(idx)]) if idx else np.zeros(0, np.int64))
-            tgts.append(np.concatenate([toff[b] + j for b, (_, j) in enumerate(idx)]) if idx else np.zeros(0, np.int64))
+            if job.pairs is not None:                             # min(Q, n_b) pairs per image: what is added to the solver's src and tgt
+                ks = [min(Q, n) for n in sizes]
+                rows.append(np.repeat(np.arange(B, dtype=np.int64) * Q, ks))
+                tgts.append(np.repeat(toff[:-1], ks))
+            else:
+                idx = _host_indices(job.indices)
+                rows.append(np.concatenate([b * Q + i for b, (i, _) in enumerate(idx)]) if idx else np.zeros(0, np.int64))
+                tgts.append(np.concatenate([toff[b] + j for b, (_, j) in enumerate(idx)]) if idx else np.zeros(0, np.int64))
             counts.append(int(rows[-1].shape[0]))
             job.B, job.Q = B, Q
         base = [0] + [int(x) for x in np.cumsum([job.B * job.Q for job in jobs])]
         n_pairs = sum(counts)
         plan = np.concatenate([np.concatenate(rows), np.concatenate([r + base[s] for s, r in enumerate(rows)]), np.concatenate(tgts),
                                np.asarray(sizes, dtype=np.int64)])
-        plan = torch.from_numpy(plan).to(dev)                     # the one host -> device copy
+        on_device = any(job.pairs is not None for job in jobs)
+        if on_device:                                             # pinned and asynchronous: the copy does not wait for the stream
+            plan = torch.from_numpy(plan).pin_memory().to(dev, non_blocking=True)
+        else:
+            plan = torch.from_numpy(plan).to(dev)                 # the one host -> device copy
         local, glob, tsel, lengths = plan[:n_pairs], plan[n_pairs:2 * n_pairs], plan[2 * n_pairs:3 * n_pairs], plan[3 * n_pairs:]
+        if on_device and n_pairs:                                 # the matched rows and target positions are formed here, from the solver's output
+            solved = torch.cat([job.pairs if job.pairs is not None else torch.zeros(2, m, dtype=torch.int64, device=dev) for job, m in zip(jobs, counts)], 1)
+            local, glob, tsel = local + solved[0], glob + solved[0], tsel + solved[1]
         starts = [0] + [int(x) for x in np.cumsum(counts)]
 
         if need_labels:
@@ -299,6 +314,8 @@ class SetCriterion(nn.Module):
         """The matcher's indices of every set.  With ``cost_matrix``: every cost matrix is computed on the device, all go to the host in one copy."""
         if not hasattr(self.matcher, "cost_matrix"):
             return [self.matcher(o, targets) for o in sets]
+        if getattr(self.matcher, "solver", "scipy") == "device":      # solved on the device, one launch per 16 sets: device index tensors, no copy
+            return self.matcher.assign_sets(sets, targets)
         from scipy.optimize import linear_sum_assignment
         with torch.no_grad():
             costs = [self.matcher.cost_matrix(o, targets) for o in sets]
@@ -343,7 +360,10 @@ class SetCriterion(nn.Module):
             matched.append(("_interm", outputs["interm_outputs"], False))
         matched += [(f"_enc_{i}", enc, False) for i, enc in enumerate(outputs.get("enc_outputs", []))]
         all_indices = self._match([o for _, o, _ in matched], targets)
-        jobs = [_Job(sfx, o, ind, num_boxes, log) for (sfx, o, log), ind in zip(matched, all_indices)]
+        all_pairs = [None] * len(matched)
+        if isinstance(all_indices, tuple):                       # the device solver: the indices as views, and the tensors they are views of
+            all_indices, all_pairs = all_indices
+        jobs = [_Job(sfx, o, ind, num_boxes, log, pairs) for (sfx, o, log), ind, pairs in zip(matched, all_indices, all_pairs)]
 
         dn_meta = outputs["dn_meta"]
         use_dn = bool(self.training and dn_meta and "output_known_lbs_bboxes" in dn_meta)

@@ -9,6 +9,7 @@ Drop-ins, by signature and result, for what the reference's detection code takes
     nms(boxes, scores, thr), batched_nms(boxes, scores, idxs, thr)      torchvision's rule and results: int64 indices by descending score
     PostProcess(num_select, nms_iou_threshold)                          the reference's list of dicts; postprocess_launch is its capturable form
     HungarianMatcher(cost_class, cost_bbox, cost_giou, focal_alpha)     the cost matrix from one kernel, one copy to the host, scipy imported lazily
+    hungarian_assign(cost, sizes), HungarianMatcher(solver="device")    the assignment itself on the device: no copy to the host
 
 The pairwise ops are forward only: an input that requires grad while grad mode is on raises (the differentiable GIoU of the losses, over matched pairs,
 lives in criterion.py).  The reference's ``generalized_box_iou`` asserts ``(boxes[:, 2:] >= boxes[:, :2]).all()``, a host synchronisation per call; it is deliberately
@@ -23,9 +24,10 @@ from torch import nn
 from . import _lib
 
 __all__ = ["box_cxcywh_to_xyxy", "box_xyxy_to_cxcywh", "box_iou", "generalized_box_iou", "nms", "batched_nms", "PostProcess", "postprocess_launch",
-           "HungarianMatcher", "NMS_MAX_BOXES", "SELECT_MAX_K"]
+           "HungarianMatcher", "hungarian_assign", "NMS_MAX_BOXES", "SELECT_MAX_K", "ASSIGN_MAX_SIDE"]
 
 NMS_MAX_BOXES = 8192
+ASSIGN_MAX_SIDE = 2048      # queries, and targets of one image, the device assignment solver takes
 SELECT_MAX_K = 1024
 _FLOATS = (torch.float32, torch.float16, torch.bfloat16)
 
@@ -228,18 +230,131 @@ class PostProcess(nn.Module):
         return results
 
 
+def _host_to_device(values, dtype, device):
+    """A host list as a device tensor through pinned memory and an asynchronous copy: no synchronisation of the stream."""
+    return torch.tensor(values, dtype=dtype).pin_memory().to(device, non_blocking=True)
+
+
+def assign_launch(costs, sizes):
+    """The solver of csrc/fvit_assign.hip on a list of dense fp32 device (B, Q, T) cost matrices that share ``sizes`` (the host list of targets per
+    image) and min(Q, n_b): ceil(len / 16) launches.  Returns (pairs, status): per set an int64 (2, P) device tensor, row 0 the queries and row 1 the
+    image-local targets, image b's k_b = min(Q, n_b) pairs at the prefix sum of k, and the int32 (len, B) status.  No device-to-host copy."""
+    who = "hungarian_assign"
+    lib = _lib.lib()
+    dev = costs[0].device
+    B, T = len(sizes), int(sum(sizes))
+    ks = None
+    for c in costs:
+        if c.dim() != 3 or c.shape[0] != B or c.shape[2] != T or c.shape[1] < 1:
+            raise RuntimeError(f"{who}: cost must be (B, Q, T) with B = {B} images, Q >= 1 and T = {T} targets (the sum of sizes), got {tuple(c.shape)}")
+        k = [min(int(c.shape[1]), n) for n in sizes]
+        if ks is not None and k != ks:
+            raise RuntimeError(f"{who}: the sets of one call share their pair offsets, so min(Q, n_b) must be the same in every set")
+        ks = k
+    P = sum(ks)
+    pairs = [torch.empty(2, P, dtype=torch.int64, device=dev) for _ in costs]
+    status = torch.zeros(len(costs), B, dtype=torch.int32, device=dev)
+    if T == 0:
+        return pairs, status
+    offs = []
+    for counts in (sizes, ks):
+        offs.append(0)
+        for n in counts:
+            offs.append(offs[-1] + n)
+    offsets = _host_to_device(offs, torch.int32, dev)             # toff [B + 1], then pair_off [B + 1]
+    toff, pair_off = offsets[:B + 1], offsets[B + 1:]
+    with torch.cuda.device(dev):
+        for lo in range(0, len(costs), _lib.FVIT_DET_MAX_SETS):
+            part = costs[lo:lo + _lib.FVIT_DET_MAX_SETS]
+            table = (_lib.FvitDetAssignSet * len(part))(*[
+                _lib.FvitDetAssignSet(cost=c.data_ptr(), src=pairs[lo + s][0].data_ptr(), tgt=pairs[lo + s][1].data_ptr(), Q=c.shape[1], T=T, n_pairs=P)
+                for s, c in enumerate(part)])
+            need = int(lib.fvit_det_assign_workspace(table, len(part), B))
+            if need == 0:
+                _lib.check(-1, "fvit_det_assign_workspace")
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            _lib.check(lib.fvit_det_assign(table, len(part), B, toff.data_ptr(), pair_off.data_ptr(), max(sizes), status[lo:lo + len(part)].data_ptr(),
+                                           ws.data_ptr(), need, _lib.stream_ptr()), "fvit_det_assign")
+    return pairs, status
+
+
+def _split_pairs(pairs, ks):
+    out, lo = [], 0
+    for k in ks:
+        out.append((pairs[0, lo:lo + k], pairs[1, lo:lo + k]))
+        lo += k
+    return out
+
+
+def hungarian_assign(cost, sizes):
+    """scipy.optimize.linear_sum_assignment of every image's block ``cost[b, :, sum(sizes[:b]) : sum(sizes[:b + 1])]`` of a device (B, Q, T) cost matrix,
+    solved on the device (csrc/fvit_assign.hip).  ``sizes`` is the host list of targets per image.  Returns ([(src, tgt)] per image, status): int64 device
+    views of one buffer, src ascending, min(Q, n_b) pairs each, and the int32 (B,) device status (0 solved; 1 a non-finite cost, the pairing is then the
+    identity; 2 / 3 see include/fvit_hip.h).  16-bit costs are widened to fp32; nothing is copied to the host."""
+    who = "hungarian_assign"
+    if not isinstance(cost, torch.Tensor):
+        raise TypeError(f"{who}: cost must be a tensor, got {type(cost).__name__}")
+    if cost.dtype == torch.float64:
+        raise RuntimeError(f"{who}: cost is float64, which is not supported (float32, float16 or bfloat16)")
+    c = _float_input(who, "cost", cost)
+    if c.dim() != 3:
+        raise RuntimeError(f"{who}: cost must be (B, Q, T), got {tuple(c.shape)}")
+    sizes = [int(n) for n in sizes]
+    if any(n < 0 for n in sizes) or not sizes:
+        raise RuntimeError(f"{who}: sizes must be a non-empty list of target counts >= 0, got {sizes}")
+    if c.shape[1] > ASSIGN_MAX_SIDE or max(sizes) > ASSIGN_MAX_SIDE:
+        raise RuntimeError(f"{who}: Q = {c.shape[1]} or an image's target count is above {ASSIGN_MAX_SIDE}, the most the solver takes a side")
+    pairs, status = assign_launch([c], sizes)
+    Q = c.shape[1]
+    return _split_pairs(pairs[0], [min(Q, n) for n in sizes]), status[0]
+
+
 class HungarianMatcher(nn.Module):
     """The reference's matcher: a 1-to-1 assignment between predictions and targets that minimises
     cost_bbox * L1 + cost_class * focal + cost_giou * (-GIoU).  The (B * Q, T) cost matrix comes from one kernel that evaluates the sigmoid and both focal
-    terms only at the gathered target classes; it goes to the host in one copy, where scipy (imported on first use) solves each image's block."""
+    terms only at the gathered target classes; it goes to the host in one copy, where scipy (imported on first use) solves each image's block.
+    ``solver="device"`` solves the blocks with ``hungarian_assign`` instead: nothing goes to the host, the indices are device tensors, and the solver's
+    status stays on the device in ``last_status`` until ``check_status()`` is asked for it."""
 
-    def __init__(self, cost_class: float = 1, cost_bbox: float = 1, cost_giou: float = 1, focal_alpha=0.25):
+    def __init__(self, cost_class: float = 1, cost_bbox: float = 1, cost_giou: float = 1, focal_alpha=0.25, solver: str = "scipy"):
         super().__init__()
         self.cost_class = cost_class
         self.cost_bbox = cost_bbox
         self.cost_giou = cost_giou
         assert cost_class != 0 or cost_bbox != 0 or cost_giou != 0, "all costs cant be 0"
         self.focal_alpha = focal_alpha
+        if solver not in ("scipy", "device"):
+            raise ValueError(f"HungarianMatcher: solver must be 'scipy' or 'device', got {solver!r}")
+        self.solver = solver
+        self.last_status = None
+
+    @torch.no_grad()
+    def assign_sets(self, output_sets, targets):
+        """The device solver on several output sets at once (one launch per 16): [[(src, tgt)] per image] per set, device tensors."""
+        sizes = [len(v["boxes"]) for v in targets]
+        costs = [self.cost_matrix(o, targets).to(torch.float32) for o in output_sets]      # the dtype round trip the scipy path sees
+        groups = {}                                        # the sets of one launch share min(Q, n_b): one group per Q
+        for s, c in enumerate(costs):
+            groups.setdefault(c.shape[1], []).append(s)
+        pairs, rows = [None] * len(costs), [None] * len(costs)
+        for members in groups.values():
+            got, status = assign_launch([costs[s] for s in members], sizes)
+            for k, s in enumerate(members):
+                pairs[s], rows[s] = got[k], status[k]
+        self.last_status = torch.stack(rows)
+        return [_split_pairs(p, [min(c.shape[1], n) for n in sizes]) for p, c in zip(pairs, costs)], pairs
+
+    def check_status(self):
+        """Synchronises, reads ``last_status`` and raises what scipy raises for a cost matrix with non-finite entries (the device solver refuses +inf
+        entries too, which scipy reports only when they make the problem infeasible)."""
+        if self.last_status is None:
+            return
+        st = self.last_status.cpu()
+        if bool((st == 1).any()):
+            where = [tuple(x) for x in (st == 1).nonzero().tolist()]
+            raise ValueError(f"matrix contains invalid numeric entries, or: cost matrix is infeasible (a non-finite cost in (set, image) {where})")
+        if bool((st != 0).any()):
+            raise RuntimeError(f"hungarian_assign: the solver gave status {sorted(set(st.flatten().tolist()) - {0})} (2: a trip bound, 3: inconsistent offsets)")
 
     @torch.no_grad()
     def cost_matrix(self, outputs, targets):
@@ -267,6 +382,8 @@ class HungarianMatcher(nn.Module):
 
     @torch.no_grad()
     def forward(self, outputs, targets):
+        if self.solver == "device":
+            return self.assign_sets([outputs], targets)[0][0]
         C = self.cost_matrix(outputs, targets).cpu()      # the single copy to the host
         from scipy.optimize import linear_sum_assignment
         sizes = [len(v["boxes"]) for v in targets]

@@ -833,6 +833,35 @@ int fvit_det_box_loss_backward(const FvitDetBoxSet* sets, int32_t n_sets, const 
 /* Refused by name (FVIT_EINVAL) before any launch, outputs untouched: n_sets outside 1 .. 16, C < 1, R < 1 or R != B * Q, R * C >= 2^31, M < 0,
  * card_stride < B, a null or misaligned pointer (floats and ints 4 bytes, boxes and the workspace 16 bytes); FVIT_EWORKSPACE for a short workspace. */
 
+/* ---- the matcher's Hungarian assignment (csrc/fvit_assign.hip) ----
+ * A batched rectangular linear-sum-assignment solver: what scipy.optimize.linear_sum_assignment(cost[b, :, toff[b]:toff[b + 1]]) returns, for every image b
+ * of up to FVIT_DET_MAX_SETS output sets in one launch (grid (B, n_sets), one wave64 per problem).  cost f32 [B][Q][T] per set; toff i32 [B + 1] (the prefix
+ * sum of the images' target counts n_b, toff[B] == T) and pair_off i32 [B + 1] (the prefix sum of k_b = min(Q, n_b)) are DEVICE memory and shared by the sets,
+ * so every set of a launch has the same k_b (all Q equal, or all at least max n_b).  max_nb is the host's statement of the largest n_b.
+ * Shortest augmenting paths with dual variables over the short side; duals and path costs in fp64, in which fp32 costs are exact, so the optimum is that of
+ * the problem scipy sees.  Ties go to the lowest path cost, then to an unassigned column, then to the lowest index: bitwise repeatable, no atomic.
+ *   src i64 [n_pairs], tgt i64 [n_pairs]: image b's k_b pairs at pair_off[b], src (the query) ascending, tgt the target's index inside the image.
+ *   status i32 [n_sets][B]: 0 solved (also n_b == 0, which writes no pair); 1 a non-finite cost (NaN, -inf or +inf, even one that scipy could route around):
+ *   not solved; 2 a loop ran into its trip bound (k augmentations, k + 1 column visits and path steps each; not reachable with finite costs); 3 the device
+ *   offsets contradict the call (n_b outside [0, max_nb], targets outside [0, T], pair_off not the prefix sum of k_b or beyond n_pairs).  Status 1 and 2
+ *   write the identity pairing src = tgt = 0 .. k_b - 1, status 3 writes no pair; nothing is read or written out of bounds.
+ * workspace: the transposed blocks of the images with n_b < Q, 4 * sum Q * T bytes rounded up to 16 (at least 16), from fvit_det_assign_workspace; 0 = refused.
+ * Refused by name (FVIT_EINVAL) before any launch, outputs untouched: n_sets outside 1 .. 16, B < 1, Q < 1, T < 0, n_pairs < 0, Q or max_nb above 2048 (the
+ * solver's state of both sides is held in 60 KiB of LDS), max_nb < 0, a null or misaligned pointer (cost and the int32 arrays 4 bytes, src and tgt 8 bytes,
+ * the workspace 16 bytes); FVIT_EWORKSPACE for a short workspace.  When every T is 0 nothing is launched and nothing is written.
+ * Nothing is allocated, there is no host synchronisation, and the call is capturable (the table is HOST memory, read during the call). */
+typedef struct FvitDetAssignSet {
+    const float* cost;  /* [B][Q][T] */
+    int64_t* src;       /* [n_pairs] */
+    int64_t* tgt;       /* [n_pairs] */
+    int32_t Q, T;
+    int32_t n_pairs;    /* the length of src and tgt: at least pair_off[B] */
+    int32_t _pad;
+} FvitDetAssignSet;
+size_t fvit_det_assign_workspace(const FvitDetAssignSet* sets, int32_t n_sets, int32_t B);
+int fvit_det_assign(const FvitDetAssignSet* sets, int32_t n_sets, int32_t B, const int32_t* toff, const int32_t* pair_off, int32_t max_nb, int32_t* status,
+                    void* workspace, size_t workspace_bytes, fvit_stream_t stream);
+
 /* Performance-experiment knobs for A/B runs inside one process; the same keys can be preset through the environment as
  * FVIT_TUNE_<key>=<int> (read once per key).  Kernel-selection knobs never change results beyond fp32 summation order:
  *   "mlp_fused", "attn_fused" 0/1; "mlp_fused_min_rows", "attn_fused_min_rows", "mlp_fused512_min_rows", "attn_fused512_min_rows";
