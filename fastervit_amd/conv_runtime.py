@@ -10,8 +10,9 @@ per-forward path:
         final BN + AdaptiveAvgPool2d(1) + head           (FV:925-927, 953-960) -> one fp32 Linear on the pooled map
     exact in real arithmetic; weights are kept as 16-bit channels_last tensors ([Cout][3][3][Cin] matrices), so there is
     no autocast and no per-forward cast of parameters.
-  * every 3x3 convolution (+ folded bias + ReLU / GELU + residual) is ONE hand-written HIP kernel (csrc/fvit_conv.hip:
-    implicit-GEMM, halo-tiled 64-channel conv, fused two-conv stem); channel counts that are not a multiple of 64 are
+  * every 3x3 convolution (+ folded bias + ReLU / GELU + residual) is ONE hand-written HIP kernel (the driver of csrc/fvit_conv.hip over
+    csrc/fvit_conv_gemm.hip: implicit GEMM, fvit_conv_halo.hip: halo-tiled 64-channel conv, fvit_conv_band.hip: row-band 128-channel conv;
+    csrc/fvit_stem.hip: fused two-conv stem); channel counts that are not a multiple of 64 are
     zero-padded to one (``pad_channels``).  MIOpen (``F.conv2d``) + the glue passes of csrc/fvit_glue.hip remain only as the
     fallback for shapes those kernels do not cover (``pad_channels = False`` or ``use_hip_conv = False``).
   * timm's LayerNorm2d (Downsample) is one HBM pass (``ln2d_kernel``) -- or, in the 16-bit classifier plan, no pass at all: it runs in the epilogue of

@@ -1,4 +1,4 @@
-"""The tile and column-group geometry of csrc/fvit_conv.hip restated in Python (edge_tiling, tile_pos, band_groups): what tests/test_conv_edge_tiles_cpu.py
+"""The tile and column-group geometry of csrc/fvit_conv.h (edge_tiling, tile_pos) and csrc/fvit_conv_band.hip (band_groups) restated in Python: what tests/test_conv_edge_tiles_cpu.py
 reasons about and what tests/test_gpu_conv_edge_tiles.py holds the driver's reported tile counts to.  No GPU, no library.
 
 conv3x3_c64_halo_kernel and stem_fused_kernel tile an H x W map with 8 x 16 tiles.  When the last tile column would hold Wr = W mod 16 in 1 .. 8 real

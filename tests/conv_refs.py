@@ -1,4 +1,4 @@
-"""References, inputs and case tables for the 3x3 conv and stem kernels of csrc/fvit_conv.hip, shared by tests/test_conv_refs_cpu.py (the proof that the
+"""References, inputs and case tables for the 3x3 conv and stem kernels of csrc/fvit_conv_*.hip and csrc/fvit_stem.hip, shared by tests/test_conv_refs_cpu.py (the proof that the
 references and the bar are fair and have teeth, no GPU), tests/test_gpu_conv_exact.py (integer inputs, exact equality) and
 tests/test_gpu_conv_values.py (random inputs against the bar).  Plain PyTorch on the CPU, nothing else.
 
@@ -21,8 +21,8 @@ erf-GELU on a grid of 1.6e6 points over [-GELU_RANGE, GELU_RANGE]; the value bui
 Measured: G = 3.80e-5 (the header documents 5.4e-5 for the fp32 evaluation; scripts/fit_gelu.py is the derivation).
 
 ``stem_fused`` (both PatchEmbed convs in one kernel) narrows ONCE: ReLU(conv1 + b1) is rounded to the map type before conv2 -- phase A's LDS store,
-csrc/fvit_conv.hip:1325-1326 (the contiguous-run gather of fp32 channels-last images) and :1429-1430 (the strided gather); phase B accumulates in
-fp32 and rounds the result once (:1486).  ``exact`` is the float64 chain with that rounding.  A conv1 value within an fp32 rounding error of a
+the ``(T)y`` of stem_fused_kernel (csrc/fvit_stem.hip) in the contiguous-run gather of fp32 channels-last images and in the strided gather; phase B
+accumulates in fp32 and rounds the result once (the ``(T)fmaxf`` of its epilogue).  ``exact`` is the float64 chain with that rounding.  A conv1 value within an fp32 rounding error of a
 rounding boundary may legitimately land on the other side, so, as tests/fused_block_refs.py does for its chains, the bar's e32 term becomes
 
     F * e16          e16 = max_i |plain32[i] - exact[i]|,  plain32 = the float32 chain rounded at the same point
@@ -338,7 +338,7 @@ GEMM_MAPS = [(3, 9, 13, 1), (3, 9, 13, 2), (2, 8, 6, 2), (2, 1, 1, 1), (2, 1, 5,
 GEMM_TILES = [(T128, 128, ()), (T128, 192, (("conv_n128_ragged", 1),)), (T64, 64, ()), (T64, 192, (("conv_n128_ragged", 0),)),
               (T256, 64, (("conv64_variant", 1),)), (T256, 192, (("conv_n128_ragged", 0), ("conv64_variant", 1)))]
 # (Cin, cin_valid): K steps straddle taps, non-empty zero tail.  376: one of the three multiples of 8 up to 448 (328, 376, 440) at which fp32 k * (1 / cv)
-# falls below the integer k / cv, i.e. at which the + 0.5 of the dense-K tap computation (fvit_conv.hip, stage_x) decides the tap
+# falls below the integer k / cv, i.e. at which the + 0.5 of the dense-K tap computation (fvit_conv_gemm.hip, stage_x) decides the tap
 DENSE_CV = [(64, 8), (64, 24), (64, 40), (128, 72), (128, 104), (256, 200), (448, 392), (448, 376)]
 PX_FORMS = [(in_lo, out) for in_lo in (False, True) for out in ("16", "lo", "f32")]
 

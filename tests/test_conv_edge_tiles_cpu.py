@@ -1,4 +1,4 @@
-"""The edge-strip tiling (tests/conv_edge_geometry.py, the restatement of csrc/fvit_conv.hip's edge_tiling / tile_pos) and the count of the band kernel's
+"""The edge-strip tiling (tests/conv_edge_geometry.py, the restatement of csrc/fvit_conv.h's edge_tiling / tile_pos) and the count of the band kernel's
 column groups that hold a real position.  CPU only; tests/test_gpu_conv_edge_tiles.py checks the restatement against the tile counts the driver reports."""
 import pytest
 

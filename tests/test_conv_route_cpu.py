@@ -128,8 +128,13 @@ def test_legacy_queries_follow_the_driver(lib):
 
 def test_the_choice_lives_in_one_place():
     src = open(os.path.join(CSRC_DIR, "fvit_conv.hip")).read()
-    for knob in ROUTE_KNOBS:
+    units = [f for f in sorted(os.listdir(CSRC_DIR)) if f.endswith((".hip", ".h"))]
+    assert {"fvit_conv.h", "fvit_conv_gemm.hip", "fvit_conv_halo.hip", "fvit_conv_band.hip", "fvit_stem.hip"} <= set(units)
+    everything = "".join(open(os.path.join(CSRC_DIR, f)).read() for f in units)
+    for knob in ROUTE_KNOBS:   # read once, in the driver: no kernel unit reads a route knob
         assert len(re.findall(r'tune_get\(\s*"%s"' % knob, src)) == 1, knob
+        assert len(re.findall(r'tune_get\(\s*"%s"' % knob, everything)) == 1, knob
+    assert "__global__" not in src and everything.count("choose_conv_route(") == src.count("choose_conv_route(")
     rt = open(os.path.join(os.path.dirname(CSRC_DIR), "conv_runtime.py")).read()
     for name in LEGACY_CALLS:
         assert not re.search(r"\b%s\b" % name, rt), name

@@ -1,4 +1,4 @@
-"""The edge strip of transposed tiles in conv3x3_c64_halo_kernel (both instances) and stem_fused_kernel (all three gathers) (csrc/fvit_conv.hip; geometry:
+"""The edge strip of transposed tiles in conv3x3_c64_halo_kernel (both instances) and stem_fused_kernel (all three gathers) (csrc/fvit_conv_halo.hip, csrc/fvit_stem.hip; geometry:
 tests/conv_edge_geometry.py).  Needs an MI355X.
 
 Three kinds of check, in fp16 and bf16:
@@ -64,7 +64,7 @@ def test_halo_integer_case_and_tile_count(shape, dt, capfd):
     B, H, W = shape
     run = L.ConvRun(c, inp, dt)
     for edge in (1, 0):
-        for act in (0, 1, 2):             # a GELU launch keeps the plain tiling: its bits depend on a pixel's row in its tile (fvit_conv.hip, run_conv)
+        for act in (0, 1, 2):             # a GELU launch keeps the plain tiling: its bits depend on a pixel's row in its tile (fvit_conv_halo.hip, launch)
             capfd.readouterr()
             with tuned(conv_halo_debug=1, conv_edge_tiles=edge):
                 got = run.run(act)["hi"]

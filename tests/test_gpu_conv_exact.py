@@ -1,4 +1,4 @@
-"""Every 3x3 conv and stem route of csrc/fvit_conv.hip on the integer cases of tests/conv_refs.py: inputs, weights, bias and residual are small
+"""Every 3x3 conv and stem route of csrc/fvit_conv_*.hip and csrc/fvit_stem.hip on the integer cases of tests/conv_refs.py: inputs, weights, bias and residual are small
 integers, every partial sum is an integer of magnitude <= 256 -- exact in fp32, fp16 and bf16 in any summation order -- so the kernel's output must
 EQUAL the reference (torch.equal on the values; -0 equals +0).  One dropped or mis-addressed (tap, channel) product at one pixel changes an integer.
 

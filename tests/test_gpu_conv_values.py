@@ -1,4 +1,4 @@
-"""The 16-bit conv and stem routes of csrc/fvit_conv.hip on random inputs, held to the bar of tests/conv_refs.py: one correct rounding to the output
+"""The 16-bit conv and stem routes of csrc/fvit_conv_*.hip and csrc/fvit_stem.hip on random inputs, held to the bar of tests/conv_refs.py: one correct rounding to the output
 type plus 8 x the error of a plain fp32 evaluation of the same sum (plus G, the documented error of the gelu_fast polynomial, for act 2), against
 float64 on the values the kernel receives.  Activations 0 / 1 / 2, without a residual, with one, and in place over it; fp16 and bf16.  Every case
 prints its worst error / bar.  tests/test_conv_refs_cpu.py shows on the CPU that other fp32 summation orders meet this bar and which errors do not.
