@@ -102,6 +102,11 @@ ProfScope::~ProfScope() {
     if (slot_ >= 0 && 2 * slot_ + 1 < (int)g_events.size()) hipEventRecord(g_events[2 * slot_ + 1], stream_);
 }
 
+bool prof_enabled() {
+    DiagLock lock(diag_mutex());
+    return g_prof_on;
+}
+
 void prof_note(const char* kernel, int grid) {
     DiagLock lock(diag_mutex());
     if (!g_prof_on || g_recs.empty()) return;
@@ -781,6 +786,15 @@ int fvit_gemm_residual(int32_t operand_dtype, const void* A, int32_t lda, const 
     return launch_gemm(g, (hipStream_t)stream);
 }
 
+int fvit_gemm_residual_add(int32_t operand_dtype, const void* A, int32_t lda, const void* Wt, int32_t ldw, const float* bias, const float* gamma,
+                           float* x, int32_t ldx, int32_t M, int32_t N, int32_t K, const float* add, const int32_t* add_idx, int32_t rows_per_image,
+                           fvit_stream_t stream) {
+    if (add && rows_per_image <= 0) { set_error("gemm_residual_add: rows_per_image %d", rows_per_image); return FVIT_EINVAL; }
+    GemmCall g = {operand_dtype, A, lda, Wt, ldw, bias, gamma, x, ldx, M, N, K, 2};
+    if (add) { g.add = add; g.add_idx = add_idx; g.rows_per_image = rows_per_image; }   // as run_mlp hands the next block's position embedding to fc2
+    return launch_gemm(g, (hipStream_t)stream);
+}
+
 int fvit_gemm_residual_splitk(int32_t operand_dtype, const void* A, int32_t lda, const void* Wt, int32_t ldw, const float* bias, const float* gamma,
                               float* x, int32_t ldx, int32_t M, int32_t N, int32_t K, float* slab, size_t slab_bytes, fvit_stream_t stream) {
     GemmCall g = {operand_dtype, A, lda, Wt, ldw, bias, gamma, x, ldx, M, N, K, 2};
@@ -810,6 +824,10 @@ int fvit_gemm_terms_lo(int32_t operand_dtype, const void* A, int32_t lda, const 
 int fvit_window_attention_terms(int32_t operand_dtype, const void* qkv, int32_t ldq, int32_t q_lo_off, void* out, int32_t ldo,
                                 int32_t o_lo_off, const float* bias, int32_t nwin, int32_t S, int32_t heads, int32_t dpad, float scale,
                                 fvit_stream_t stream) {
+    if (!attention_dense(S, dpad)) {   // as fvit_window_attention: the long kernel takes the compact table, a dense `bias` would be dropped without a word
+        set_error("window_attention_terms: S=%d at dpad=%d is outside the dense-bias kernel (fvit_attention_dense); use fvit_window_attention_long_terms", S, dpad);
+        return FVIT_EINVAL;
+    }
     AttnCall a = {operand_dtype, qkv, ldq, out, ldo, bias, nwin, S, heads, dpad, scale, nullptr, 0, 0, 0};
     a.q_lo_off = q_lo_off;
     a.o_lo_off = o_lo_off;

@@ -21,6 +21,8 @@
 //     fragment.  V^T rows are assigned to A-row slots so that a lane ends up with 8 (dpad 32) or
 //     16 (dpad 64) consecutive output channels: 16/32-byte stores.
 //   * Padded key columns carry FVIT_MASK_BIAS in the folded bias table, so masking costs nothing.
+#include <cstdio>
+
 #include "fvit_common.h"
 
 namespace fvit {
@@ -336,7 +338,11 @@ int launch_attention(const AttnCall& c, hipStream_t stream) {
     const double flops = 4.0 * c.nwin * (double)c.heads * c.S * (double)c.S * (c.d > 0 && c.d <= c.dpad ? c.d : c.dpad);
     const double bytes = 2.0 * c.nwin * (double)c.S * c.heads * c.dpad * 4.0;  // q,k,v read + o write (16-bit)
     ProfScope prof(FVIT_K_ATTENTION, flops, bytes, stream);
-    prof_note(tt ? "attn_kernel<two-term>" : "attn_kernel", tt ? (c.nwin * c.heads + 1) / 2 : (c.nwin * c.heads + 3) / 4);
+    if (prof_enabled()) {   // the launch name carries the instance: "attn_kernel[<two-term>] sb<SB> dp<DP>", SB after the 9 -> 10 and 11, 12 -> 13 remaps above
+        char name[40];
+        snprintf(name, sizeof(name), "%s sb%d dp%d", tt ? "attn_kernel<two-term>" : "attn_kernel", sb, c.dpad);
+        prof_note(name, tt ? (c.nwin * c.heads + 1) / 2 : (c.nwin * c.heads + 3) / 4);
+    }
 #define FVIT_ATTN_DP(T) (c.dpad == 32 ? launch_sb<T, 32>(p, sb, stream) : c.dpad == 64 ? launch_sb<T, 64>(p, sb, stream) : launch_sb<T, 96>(p, sb, stream))
     if (c.dtype == FVIT_F16) return FVIT_ATTN_DP(_Float16);
     if (c.dtype == FVIT_BF16) return FVIT_ATTN_DP(__bf16);

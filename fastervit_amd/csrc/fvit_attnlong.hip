@@ -26,6 +26,8 @@
 // q_lo_off), scores = kh.qh + kl.qh + kh.ql, the tile's probabilities are split in registers (ph = round(e), pl = round(e - ph); the running sum takes
 // the fp32 e), O += vh.ph + vl.ph + vh.pl with both V^T images in LDS, and the output leaves as hi + lo (lo at column o_lo_off).  This is what the
 // 21k 384 / 512 / 768 fine-tunes (one window of 24^2 .. 48^2 tokens) and large carrier grids needed to run the ABSOLUTE-tolerance plan (missing 6).
+#include <cstdio>
+
 #include "fvit_common.h"
 
 namespace fvit {
@@ -287,7 +289,11 @@ int launch_long_t(AttnLongParams& p, hipStream_t stream) {
         set_error("attention(long): grid too large");
         return FVIT_EINVAL;
     }
-    prof_note(TT ? "attn_long_kernel<two-term>" : "attn_long_kernel", (int)grid);
+    if (prof_enabled()) {
+        char name[40];
+        snprintf(name, sizeof(name), "%s dp%d", TT ? "attn_long_kernel<two-term>" : "attn_long_kernel", DP);
+        prof_note(name, (int)grid);
+    }
     hipLaunchKernelGGL((attn_long_kernel<T, DP, TT>), dim3((unsigned)grid), dim3(256), lds, stream, p);
     return check_launch("attn_long_kernel");
 }

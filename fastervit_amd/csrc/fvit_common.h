@@ -40,6 +40,10 @@ template <> struct Op16<__bf16> {
 template <typename T> __device__ __forceinline__ T sat16(float x);
 template <> __device__ __forceinline__ _Float16 sat16<_Float16>(float x) { return (_Float16)__builtin_amdgcn_fmed3f(x, -65504.0f, 65504.0f); }
 template <> __device__ __forceinline__ __bf16 sat16<__bf16>(float x) { return (__bf16)x; }
+// sat16 that keeps a NaN: v_med3_f32 returns the smallest operand when one is a NaN, so sat16<_Float16>(NaN) is -65504 -- a NaN pre-activation would leave a
+// 16-bit epilogue as a large finite number.  The unit GEMM epilogues store through this form (tests/test_gpu_gemm_exact.py:
+// test_gemm_nan_in_an_operand_comes_back_nan); the fused kernels keep sat16 (one compare and select per stored value on their VALU-bound epilogues).
+template <typename T> __device__ __forceinline__ T sat16_nan(float x) { const T r = sat16<T>(x); return x != x ? (T)x : r; }
 
 // Cross-row lane exchanges on the VALU (gfx950 v_permlane16_swap / v_permlane32_swap) instead of __shfl_xor, which is
 // ds_bpermute_b32 -- an LDS-pipeline instruction.  r02 finding (profiles/r02_repeatability_hunt.log): in kernels that have LDS-DMA
@@ -159,24 +163,18 @@ __device__ __forceinline__ void rowmap_store8(void* px, const float (&y)[8], int
     }
 }
 
-// erf with |error| <= 1.5e-7 (Abramowitz & Stegun 7.1.26): far below the 16-bit rounding of any GELU
-// output here, branch-free and much cheaper than libm erff inside fused epilogues.
-__device__ __forceinline__ float fast_erf(float x) {
-    const float ax = fabsf(x);
-    const float t = __frcp_rn(1.0f + 0.3275911f * ax);
-    float y = 1.061405429f;
-    y = y * t - 1.453152027f;
-    y = y * t + 1.421413741f;
-    y = y * t - 0.284496736f;
-    y = y * t + 0.254829592f;
-    y = 1.0f - y * t * __expf(-ax * ax);
-    return copysignf(y, x);
-}
 // nn.GELU() (exact-erf form, AR:403) without transcendentals: erf(z) ~ z * Q(z^2) on |z| <= 3 (degree-8 minimax fit,
-// |erf error| <= 2.6e-5 incl. the clamp tail 1 - erf(3) = 2.2e-5), GELU absolute error <= 5.4e-5 for all x -- an order of
+// |erf error| <= 2.6e-5 incl. the clamp tail 1 - erf(3) = 2.2e-5), GELU absolute error <= 5.4e-5 on |x| <= 10.4 (below) -- an order of
 // magnitude below the 16-bit rounding of the value it feeds (scripts/fit_gelu.py reproduces the fit and the bound).
 // 14 plain VALU ops (SLP-packable into v_pk_fma_f32) instead of ~23 issue-cycle equivalents with rcp + exp: the fused
 // epilogues are VALU-bound, not MFMA-bound, on this term.
+// Outside |z| <= 3 the clamp of z leaves hx * (1 + z Q(9)): the positive tail x (1 - 0.52e-5) is a RELATIVE error far below a 16-bit rounding, the
+// NEGATIVE tail is -0.52e-5 |x| where GELU is 0 -- inside 5.4e-5 down to x = -10.4, -1.3e-3 at x = -256 (tests/test_gpu_gemm_exact.py found it).
+// gelu_fast_clamp_each holds x at -3 sqrt(2) first (the polynomial gives -2.2e-5 there against a true -4.7e-5 that only rises to 0) and meets 5.4e-5
+// for every x; the unit GEMM epilogues use it.  The fused MLP and conv epilogues keep the form without it: one more VALU operation per value measured
+// -1.2 % images/s on FasterViT-0 (profiles/gemm_attention_exact_tests.log), for pre-activations below -10 that a trained network's fc1 / conv outputs
+// do not reach and an error that stays below one 16-bit rounding of the activations next to it down to x = -50.
+constexpr float GELU_FAST_XMIN = -4.2426405f;
 __device__ __forceinline__ float gelu_fast(float x) {
     const float z = __builtin_amdgcn_fmed3f(x * 0.70710678118654752f, -3.0f, 3.0f);
     const float u = z * z;
@@ -258,37 +256,33 @@ __device__ __forceinline__ void gelu_fast_each(float (&x)[M]) {
     }
 }
 
-// the same function through fast_erf (|erf error| <= 1.5e-7): the two-term-activation mode (weight_terms 3) carries ~22 significant
-// bits through every Linear layer, the polynomial above would be its error floor
-__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + fast_erf(x * 0.70710678118654752f)); }
-// gelu_erf over N values in lockstep (the two-term-activation epilogues): the same operations per value, the steps pinned like gelu_fast_n
+// gelu_fast_each with x held at GELU_FAST_XMIN first (above): GELU absolute error <= 5.4e-5 for every x.  The hold is a compare and select, NOT fmaxf:
+// fmaxf drops a NaN operand (v_max_f32 returns the other one), and a NaN pre-activation -- NaN / Inf in an operand, an overflowed sum -- must leave the
+// epilogue as NaN, not as a plausible -2.2e-5 (tests/test_gpu_gemm_exact.py: test_gemm_nan_in_an_operand_comes_back_nan).
+template <int M>
+__device__ __forceinline__ void gelu_fast_clamp_each(float (&x)[M]) {
+#pragma unroll
+    for (int i = 0; i < M; ++i) x[i] = x[i] < GELU_FAST_XMIN ? GELU_FAST_XMIN : x[i];
+    gelu_fast_each<M>(x);
+}
+
+// nn.GELU() for the two-term-activation mode (weight_terms 3), which carries ~22 significant bits through every Linear layer: the polynomial above
+// would be its error floor, and so was the Abramowitz-Stegun 7.1.26 erf used before -- its 1.5e-7 is an ABSOLUTE erf error, GELU multiplies it by 0.5 |x| (2.2e-7 at x = -3.25, where GELU
+// itself is -1.9e-3), and 1 + erf(z) cancels for z < 0 (tests/test_gpu_gemm_exact.py: test_gemm_two_term_gelu_output).  Written on erfc of |x| / sqrt(2)
+// instead, with the library erfcf (a few ulp RELATIVE): x < 0: 0.5 x erfc, x >= 0: x - 0.5 x erfc -- no cancellation on either side, the error is a few
+// 2^-24 |GELU| plus one rounding of x.  These epilogues run behind three times the MFMA work of the 16-bit modes.
+// Non-finite x: NaN gives NaN; +inf gives +inf and -inf gives -0 (the limits; the products inf * erfc(inf) = inf * 0 would be NaN).
+__device__ __forceinline__ float gelu_erf(float x) {
+    const float ax = fabsf(x);
+    if (ax == __builtin_inff()) return x > 0.0f ? x : -0.0f;
+    const float h = 0.5f * x * erfcf(ax * 0.70710678118654752f);
+    return x < 0.0f ? h : x - h;
+}
+// gelu_erf over N values (the two-term-activation epilogues): the same operations per value
 template <int N>
 __device__ __forceinline__ void gelu_erf_n(float (&x)[N]) {
-    float ax[N], t[N], y[N], e[N];
 #pragma unroll
-    for (int i = 0; i < N; ++i) ax[i] = fabsf(x[i] * 0.70710678118654752f);
-#pragma unroll
-    for (int i = 0; i < N; ++i) t[i] = __frcp_rn(1.0f + 0.3275911f * ax[i]);
-#pragma unroll
-    for (int i = 0; i < N; ++i) e[i] = __expf(-ax[i] * ax[i]);
-    pin_values(t);
-#pragma unroll
-    for (int i = 0; i < N; ++i) y[i] = 1.061405429f * t[i] - 1.453152027f;
-    pin_values(y);
-#pragma unroll
-    for (int i = 0; i < N; ++i) y[i] = y[i] * t[i] + 1.421413741f;
-    pin_values(y);
-#pragma unroll
-    for (int i = 0; i < N; ++i) y[i] = y[i] * t[i] - 0.284496736f;
-    pin_values(y);
-#pragma unroll
-    for (int i = 0; i < N; ++i) y[i] = y[i] * t[i] + 0.254829592f;
-    pin_values(y);
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        const float r = copysignf(1.0f - y[i] * t[i] * e[i], x[i] * 0.70710678118654752f);
-        x[i] = 0.5f * x[i] * (1.0f + r);
-    }
+    for (int i = 0; i < N; ++i) x[i] = gelu_erf(x[i]);
 }
 template <int M>
 __device__ __forceinline__ void gelu_erf_each(float (&x)[M]) {
@@ -361,6 +355,7 @@ struct ProfScope {
 // names the launch the innermost live ProfScope brackets: kernel family + launch shape (workgroups), so that the per-launch records
 // (fvit_prof_records) can be matched with a rocprofv3 kernel trace / PMC row of the same (kernel, grid).  No-op when the timer is off.
 void prof_note(const char* kernel, int grid);
+bool prof_enabled();   // fvit_prof_enable(1) is active: a launcher that formats its launch name does so only then
 #ifdef FVIT_DIAG
 void dbg_poison_before_launch(hipStream_t st);   // diagnosis: register / LDS poison kernel in front of every launch (fvit_debug_poison_launches)
 void dbg_rowhash(const char* tag, const void* ptr, long long rows, int row_bytes, hipStream_t st);   // no-op unless fvit_debug_rowhash_begin is active

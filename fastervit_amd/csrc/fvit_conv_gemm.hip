@@ -348,7 +348,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_kernel(ConvParams p) {
     const T* R = (const T*)p.res;
     if constexpr (PX) {
         // two-term maps: the residual is hi + lo (fp32 sum), the result leaves as hi = round(y), lo = round(y - hi) -- or as one fp32 map for a
-        // consumer that is not an MFMA operand (the next transformer level's partition).  GELU by the 1.5e-7 erf: the polynomial's 5e-5 is a
+        // consumer that is not an MFMA operand (the next transformer level's partition).  GELU by gelu_erf (erfc form, a few ulp): the polynomial's 5e-5 is a
         // systematic error of the same size as the roundings this path removes.
         const T* RL = (const T*)p.res_lo;
         T* OL = (T*)p.out_lo;

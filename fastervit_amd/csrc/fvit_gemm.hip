@@ -21,6 +21,7 @@
 //     tiles ordered n-fastest, so the activation tile is fetched from HBM once per XCD L2 and the
 //     (small) weight matrix stays L2 resident.
 #include <algorithm>
+#include <cstdio>
 
 #include "fvit_common.h"
 
@@ -349,18 +350,18 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void gemm_kernel(GemmPara
                         for (int r = 0; r < 4; ++r) y[ni * 4 + r] = a[r] + bias[ni * 4 + r];
                     }
                     if constexpr (EPI == 1) {   // 16 values as two groups of 8 interleaved chains (fvit_common.h), bitwise the per-value functions
-                        if constexpr (LO) gelu_erf_each<16>(y); else gelu_fast_each<16>(y);
+                        if constexpr (LO) gelu_erf_each<16>(y); else gelu_fast_clamp_each<16>(y);
                     }
                     v8 o0, o1;
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) { o0[j] = sat16<T>(y[j]); o1[j] = sat16<T>(y[8 + j]); }
+                    for (int j = 0; j < 8; ++j) { o0[j] = sat16_nan<T>(y[j]); o1[j] = sat16_nan<T>(y[8 + j]); }
                     T* po = O + (size_t)m * p.ldo + nb;
                     *(v8*)po = o0;
                     *(v8*)(po + 8) = o1;
                     if constexpr (LO) {   // two-term activations (weight_terms 3): the rounding remainder as a second 16-bit term
                         v8 l0, l1;
 #pragma unroll
-                        for (int j = 0; j < 8; ++j) { l0[j] = sat16<T>(y[j] - (float)o0[j]); l1[j] = sat16<T>(y[8 + j] - (float)o1[j]); }
+                        for (int j = 0; j < 8; ++j) { l0[j] = sat16_nan<T>(y[j] - (float)o0[j]); l1[j] = sat16_nan<T>(y[8 + j] - (float)o1[j]); }
                         *(v8*)(po + p.lo_off) = l0;
                         *(v8*)(po + p.lo_off + 8) = l1;
                     }
@@ -579,18 +580,18 @@ __global__ __launch_bounds__(512, 1) void gemm_pp_kernel(GemmParams p) {
                         for (int r = 0; r < 4; ++r) y[ni * 4 + r] = a[r] + bias[ni * 4 + r];
                     }
                     if constexpr (EPI == 1) {   // 16 values as two groups of 8 interleaved chains (fvit_common.h), bitwise the per-value functions
-                        if constexpr (LO) gelu_erf_each<16>(y); else gelu_fast_each<16>(y);
+                        if constexpr (LO) gelu_erf_each<16>(y); else gelu_fast_clamp_each<16>(y);
                     }
                     v8 o0, o1;
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) { o0[j] = sat16<T>(y[j]); o1[j] = sat16<T>(y[8 + j]); }
+                    for (int j = 0; j < 8; ++j) { o0[j] = sat16_nan<T>(y[j]); o1[j] = sat16_nan<T>(y[8 + j]); }
                     T* po = O + (size_t)m * p.ldo + nb;
                     *(v8*)po = o0;
                     *(v8*)(po + 8) = o1;
                     if constexpr (LO) {
                         v8 l0, l1;
 #pragma unroll
-                        for (int j = 0; j < 8; ++j) { l0[j] = sat16<T>(y[j] - (float)o0[j]); l1[j] = sat16<T>(y[8 + j] - (float)o1[j]); }
+                        for (int j = 0; j < 8; ++j) { l0[j] = sat16_nan<T>(y[j] - (float)o0[j]); l1[j] = sat16_nan<T>(y[8 + j] - (float)o1[j]); }
                         *(v8*)(po + p.lo_off) = l0;
                         *(v8*)(po + p.lo_off + 8) = l1;
                     }
@@ -691,10 +692,12 @@ int launch_t(const GemmCall& c, hipStream_t stream) {
     // both terms of both operands -- four tiles for the same three products, and 24 instead of 16 MFMAs behind every barrier
     const bool x3 = c.K == 3 * p.ka && c.lda >= 2 * p.ka && (pp || !big) && splits == 1 && !nw8 && !p.stagger && tune_get("gemm_x3_dual", 1);
     p.x3 = x3 ? 1 : 0;
-    prof_note(c.epilogue == 2 ? (pp ? "gemm_pp_kernel<2> 256x256" : big ? "gemm_kernel<2> 256x256" : small ? "gemm_kernel<2> 64-row" : "gemm_kernel<2> 128-row")
-                              : c.epilogue == 1 ? (pp ? "gemm_pp_kernel<1> 256x256" : big ? "gemm_kernel<1> 256x256" : small ? "gemm_kernel<1> 64-row" : "gemm_kernel<1> 128-row")
-                                                : (pp ? "gemm_pp_kernel<0> 256x256" : big ? "gemm_kernel<0> 256x256" : small ? "gemm_kernel<0> 64-row" : "gemm_kernel<0> 128-row"), grid);
-    if (splits > 1) prof_note(small ? "gemm_kernel<2> 64-row split-K" : "gemm_kernel<2> 128-row split-K", grid);
+    if (prof_enabled()) {   // the launch name: "<kernel><epilogue> <tile form>[ split-K][ nw8][ x3][ xr2][ stagger]" -- every choice made above, so that a test can confirm its route
+        char name[40];
+        snprintf(name, sizeof(name), "%s<%d> %s%s%s%s%s%s", pp ? "gemm_pp_kernel" : "gemm_kernel", c.epilogue, big ? "256x256" : small ? "64-row" : "128-row",
+                 splits > 1 ? " split-K" : "", nw8 ? " nw8" : "", x3 ? " x3" : "", pp && !x3 && !xr3 ? " xr2" : "", p.stagger ? " stagger" : "");
+        prof_note(name, grid);
+    }
     // (measured r01 / r03: 3- and 4-deep rings with counted vmcnt gave no gain over 2 stages at 64..392 workgroups, and their instances missed the 2-waves-per-SIMD
     // register target; the opt-in knobs "gemm_3stage_max_grid" / "gemm_ring" and those instances were removed in r06: git history, profiles/HISTORY.md)
 #define FVIT_GEMM(E, NS, MI_, NW_) hipLaunchKernelGGL((gemm_kernel<T, E, NS, MI_, NW_>), dim3(grid), dim3(64 * NW_), 0, stream, p)

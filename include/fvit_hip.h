@@ -283,6 +283,13 @@ int fvit_gemm_residual(int32_t operand_dtype, const void* A, int32_t lda, const 
                        const float* bias, const float* gamma, float* x, int32_t ldx, int32_t M,
                        int32_t N, int32_t K, fvit_stream_t stream);
 
+/* fvit_gemm_residual with the row table of the residual epilogue: after the update, x[m][:] += add[i][:] with p = m % rows_per_image and
+ * i = add_idx ? add_idx[p] : p; a negative i adds nothing.  add: f32 rows of N floats, add_idx: device int32 [rows_per_image] or NULL.  add == NULL
+ * is fvit_gemm_residual.  (The stage path applies the next block's position embedding this way in the fc2 GEMM of the current block.) */
+int fvit_gemm_residual_add(int32_t operand_dtype, const void* A, int32_t lda, const void* Wt, int32_t ldw, const float* bias, const float* gamma,
+                           float* x, int32_t ldx, int32_t M, int32_t N, int32_t K, const float* add, const int32_t* add_idx, int32_t rows_per_image,
+                           fvit_stream_t stream);
+
 /* fvit_gemm_residual with an fp32 scratch for deterministic split-K (r04): when the 128 x 128 tile grid is small (<= 230 workgroups) and K is long
  * (>= 8 K tiles of 64), `splits` (2 .. 8) x the workgroups each accumulate 1 / splits of K into slab [splits][M][N], and a second launch adds the
  * partials in split order and applies bias / gamma / the residual update: no atomics, bitwise repeatable; the result differs from the unsplit
@@ -302,9 +309,9 @@ int fvit_gemm_terms(int32_t operand_dtype, const void* A, int32_t lda, const voi
  *   fvit_gemm_terms_lo            fvit_gemm_terms with K = 3 * ka allowed: weights [hi | lo | hi] against activation columns
  *                                 [hi | hi | lo] (A is [..][lda >= 2 * ka]) = hi.hi + hi_a.lo_w + lo_a.hi_w, the lo.lo product dropped;
  *                                 out_lo_off > 0 (epilogues 0 / 1): the output is stored as two terms too; GELU then uses the
- *                                 1.5e-7-accurate erf instead of the 5e-5 polynomial;
+ *                                 erfc form (library erfcf, a few ulp) instead of the 5e-5 polynomial;
  *   fvit_window_attention_terms   fvit_window_attention on two-term q / k / v (scores qh.kh + qh.kl + ql.kh; P and V as two terms in
- *                                 registers / LDS), output rows [hi | lo].  Dense windows (fvit_attention_dense);
+ *                                 registers / LDS), output rows [hi | lo].  Dense windows only (fvit_attention_dense; any other geometry: FVIT_EINVAL);
  *   fvit_window_attention_long_terms (r06) the same on windows beyond the dense kernel: fvit_window_attention_long with two-term q / k / v, the tile's
  *                                 probabilities split in registers, both V^T images in LDS, output rows [hi | lo] (the 21k 384 / 512 / 768 fine-tunes).
  * The reference computes these in fp32 (FV:557-568, 398-407); this is the route to logits max-abs < 1e-3 ABSOLUTE on the deep /
@@ -506,7 +513,7 @@ int fvit_global_avgpool_cl(int32_t dtype, const void* in, float* out, int32_t B,
  *              to a transformer level, one fp32 map -- a rounded stored stream costs 3-4e-4 of logits error each on FasterViT-4, a rounded conv
  *              operand 2-8e-5 (tests/tools/conv_precision_sim.py).  in_lo (needs terms 2): in.w_hi + in.w_lo + in_lo.w_hi; residual planes are
  *              added in fp32; out_lo = round(y - hi); out_f32 instead of out / out_lo.  px = 1 asks for these kernels without any of the planes
- *              (their GELU is the 1.5e-7-accurate erf form, the 16-bit kernels use a 5e-5 polynomial)
+ *              (their GELU is the erfc form on the library erfcf, the 16-bit kernels use a 5e-5 polynomial)
  *   ln_w, ln_b, ln_eps
  *              f32 [Cout] or NULL.  Set: out = LayerNorm2d(round16(conv + bias + residual)) * ln_w + ln_b over the channels of a pixel -- the
  *              following Downsample's LayerNorm2d of exactly the 16-bit map the plain kernel stores (fp32 statistics, two passes) without that

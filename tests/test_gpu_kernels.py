@@ -8,6 +8,7 @@ import torch.nn.functional as F
 
 from fastervit_amd import _lib, hat_runtime
 from oracle import hat_reference as hr
+from tests.util import tuned
 
 pytestmark = pytest.mark.gpu
 
@@ -327,11 +328,10 @@ def test_mlp_fused(opname, dt, code, M, use_gamma, C):
     # C = 512; C = 256 always runs the plain loop, the knob is a no-op there)
     outs = {}
     for pipe in (0, 1):
-        _lib.tune("win_mlp_pipe", pipe)
         xw = torch.cat([x0, torch.full((5, C), float("nan"), device="cuda")])   # rows beyond M stay untouched
-        rc = lib.fvit_win_mlp_fused(code, xw.data_ptr(), M, C, hid, lnw.data_ptr(), lnb.data_ptr(), ctypes.c_float(1e-5), w1p.data_ptr(),
-                                    b1.data_ptr(), w2c.data_ptr(), b2.data_ptr(), gamma.data_ptr() if use_gamma else None, _stream())
-        _lib.tune("win_mlp_pipe", 1)
+        with tuned(win_mlp_pipe=pipe):
+            rc = lib.fvit_win_mlp_fused(code, xw.data_ptr(), M, C, hid, lnw.data_ptr(), lnb.data_ptr(), ctypes.c_float(1e-5), w1p.data_ptr(),
+                                        b1.data_ptr(), w2c.data_ptr(), b2.data_ptr(), gamma.data_ptr() if use_gamma else None, _stream())
         _lib.check(rc, "win_mlp_fused")
         torch.cuda.synchronize()
         assert torch.isfinite(xw[:M]).all() and torch.isnan(xw[M:]).all()
@@ -404,12 +404,9 @@ def test_conv3x3_fused(dt, code, B, Ci, Co, H, W, stride, act, res):
         assert torch.equal(r2, out)
     if Co % 128 == 64 and Co > 128:   # the 128 x 64-tile walk (fvit_tune conv_n128_ragged = 0) sums every output over the same K steps: same bits
         out2 = torch.full_like(out, float("nan"))
-        try:
-            _lib.tune("conv_n128_ragged", 0)
+        with tuned(conv_n128_ragged=0):
             _lib.check(lib.fvit_conv3x3_nhwc(code, x.data_ptr(), wk.data_ptr(), bias.data_ptr(), r.data_ptr() if res else None, out2.data_ptr(), B, H, W,
                                              Ci, Co, stride, act, zeros.data_ptr(), _stream()), "conv3x3 128x64 tiles")
-        finally:
-            _lib.tune("conv_n128_ragged", 1)
         torch.cuda.synchronize()
         assert torch.equal(out2, out)
 
@@ -509,10 +506,8 @@ def test_conv3x3_patch_form(dt, code, B, Ci, Co, H, W, act, res, terms):
     wk = cl(wh) if terms == 1 else torch.cat([cl(wh), cl(wl)], dim=1).contiguous()
     zeros = torch.zeros(256, dtype=dt, device="cuda")
     outs = {}
-    try:
-        for form in (0, 1):
-            _lib.tune("conv_patch", form)
-            _lib.tune("conv_patch_max_waste_pct", 100000)
+    for form in (0, 1):
+        with tuned(conv_patch=form, conv_patch_max_waste_pct=100000):
             assert lib.fvit_conv3x3_patch_form(B, H, W, Ci, Co, 1) == form
             out = torch.full((B, Co, H, W), float("nan"), dtype=dt, device="cuda").contiguous(memory_format=torch.channels_last)
             _lib.check(lib.fvit_conv3x3_nhwc_terms(code, x.data_ptr(), wk.data_ptr(), bias.data_ptr(), r.data_ptr() if res else None, out.data_ptr(),
@@ -525,10 +520,8 @@ def test_conv3x3_patch_form(dt, code, B, Ci, Co, H, W, act, res, terms):
                                                        act, terms, zeros.data_ptr(), _stream()), "conv3x3 patch in place")
                 torch.cuda.synchronize()
                 assert torch.equal(r2, out)
-        assert lib.fvit_conv3x3_patch_form(B, H, W, Ci, Co, 2) == 0        # stride 2: never the patch form
-    finally:
-        _lib.tune("conv_patch", 1)
-        _lib.tune("conv_patch_max_waste_pct", 10)
+            if form == 1:
+                assert lib.fvit_conv3x3_patch_form(B, H, W, Ci, Co, 2) == 0        # stride 2: never the patch form
     wref = (wh.float() + wl.float()) if terms == 2 else wh.float()
     ref = F.conv2d(x.float(), wref.cuda(), bias, 1, 1)
     ref = [lambda t: t, torch.relu, F.gelu][act](ref)
@@ -597,18 +590,13 @@ def test_conv3x3_halo_matches_implicit_gemm_kernel(B, H, W, grid):
     bias = torch.randn(64, generator=g).cuda()
     zeros = torch.zeros(256, dtype=torch.float16, device="cuda")
     outs = []
-    try:
-        for halo in (0, 1):
-            _lib.tune("conv_halo", halo)
-            _lib.tune("conv_halo_grid", grid)
+    for halo in (0, 1):
+        with tuned(conv_halo=halo, conv_halo_grid=grid):
             o = torch.full_like(x, float("nan"))
             _lib.check(lib.fvit_conv3x3_nhwc(1, x.data_ptr(), wk.data_ptr(), bias.data_ptr(), r.data_ptr(), o.data_ptr(), B, H, W, 64, 64, 1, 2,
                                              zeros.data_ptr(), _stream()), "conv3x3")
             torch.cuda.synchronize()
             outs.append(o.float())
-    finally:
-        _lib.tune("conv_halo", 1)
-        _lib.tune("conv_halo_grid", 512)
     assert torch.isfinite(outs[1]).all()
     assert (outs[0] - outs[1]).abs().max().item() <= 2e-3 * max(outs[0].abs().max().item(), 1.0)
 
@@ -784,10 +772,8 @@ def test_attn_block_fused(opname, dt, code, S, nwin, use_tables, use_gamma, C):
         assert torch.isfinite(out_win).all()
         assert (out_win - ref).abs().max().item() < tol, f"win_block: {(out_win - ref).abs().max().item()} vs {tol}"
     if S > 48 and C == 256:   # r06: the wave-per-(window, head) cut (fvit_attnblk2.hip) behind fvit_tune "ab_variant" = 3, one and two windows per workgroup
-        try:
-            for nw in (1, 2):
-                _lib.tune("ab_variant", 3)
-                _lib.tune("ab2_nwin", nw)
+        for nw in (1, 2):
+            with tuned(ab_variant=3, ab2_nwin=nw):
                 o3 = torch.full((rows, C), float("nan"), device="cuda")
                 _lib.check(lib.fvit_attn_block_fused(*args, o3.data_ptr(), nwin, S, heads, C, ctypes.c_float(scale), _stream()), "attn_block_fused (attnblk2)")
                 torch.cuda.synchronize()
@@ -797,9 +783,6 @@ def test_attn_block_fused(opname, dt, code, S, nwin, use_tables, use_gamma, C):
                 _lib.check(lib.fvit_attn_block_fused(*args, o4.data_ptr(), nwin, S, heads, C, ctypes.c_float(scale), _stream()), "attn_block_fused (attnblk2)")
                 torch.cuda.synchronize()
                 assert torch.equal(o3, o4)   # fixed reduction order: bitwise repeatable
-        finally:
-            _lib.tune("ab_variant", 0)
-            _lib.tune("ab2_nwin", 1)
     if S > 48 and C == 512:   # r03: the 16 heads split over two sibling workgroups that meet in L2 (last-arriver reduction in split order)
         slab = torch.full((nwin * 2 * 64 * C,), float("nan"), device="cuda")
         cnt = torch.zeros(nwin, dtype=torch.int32, device="cuda")
@@ -857,13 +840,12 @@ def test_ct_block_fused(opname, dt, code, batch, G, use_add, use_gamma):
     scale = d ** -0.5
     p = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
     for variant in (0, 1, 2, 3):   # 3: the 8-wave form (waves split output channels)
-        _lib.tune("ct_variant", variant)
         out.fill_(float("nan"))
-        rc = lib.fvit_ct_block_fused(code, X.data_ptr(), rowsA, src_idx.data_ptr(), p(add), out.data_ptr(), batch, G, heads, C, hid,
-                                     ln1w.data_ptr(), ln1b.data_ptr(), wqf.data_ptr(), bqh.data_ptr(), wpf.data_ptr(), bproj.data_ptr(), p(g1),
-                                     bp.data_ptr(), ctypes.c_float(scale), ln2w.data_ptr(), ln2b.data_ptr(), w1f.data_ptr(), b1.data_ptr(),
-                                     w2f.data_ptr(), b2.data_ptr(), p(g2), ctypes.c_float(1e-5), _stream())
-        _lib.tune("ct_variant", 3)   # the default
+        with tuned(ct_variant=variant):
+            rc = lib.fvit_ct_block_fused(code, X.data_ptr(), rowsA, src_idx.data_ptr(), p(add), out.data_ptr(), batch, G, heads, C, hid,
+                                         ln1w.data_ptr(), ln1b.data_ptr(), wqf.data_ptr(), bqh.data_ptr(), wpf.data_ptr(), bproj.data_ptr(), p(g1),
+                                         bp.data_ptr(), ctypes.c_float(scale), ln2w.data_ptr(), ln2b.data_ptr(), w1f.data_ptr(), b1.data_ptr(),
+                                         w2f.data_ptr(), b2.data_ptr(), p(g2), ctypes.c_float(1e-5), _stream())
         _lib.check(rc, "ct_block_fused")
         torch.cuda.synchronize()
         ct = X.view(batch, rowsA, C)[:, src_idx.long()]

@@ -14,13 +14,11 @@ import torch
 import torch.nn.functional as F
 
 from fastervit_amd import _lib, hat_runtime
-from tests.util import build_product_model, case_input, load_golden, max_abs
+from tests.util import build_product_model, case_input, load_golden, max_abs, tuned
 
 pytestmark = pytest.mark.gpu
 
 OPS = [("f16", torch.float16, 1), ("bf16", torch.bfloat16, 2)]
-GEMM_PP_DEFAULT = 1      # default of the "gemm_pp" tuning knob (fvit_gemm.hip)
-CT_VARIANT_DEFAULT = 3   # default of the "ct_variant" knob (fvit_ctblk.hip)
 
 
 def _rup(x, m):
@@ -246,7 +244,6 @@ def test_gemm_256x256_tile(opname, dt, code, M, N, K, epi, pp):
     N not a multiple of 64) and the FasterViT-4 layer shapes: same contract as the 128 x 128 tile, compared against it and fp32 torch.
     pp = 1: the ping-pong form of that tile (gemm_pp_kernel: two wave groups alternate between MFMA and LDS / request sections)."""
     lib = _lib.lib()
-    _lib.tune("gemm_pp", pp)
     g = torch.Generator(device="cpu").manual_seed(M + N + K + epi)
     A = torch.randn(M, K, generator=g).to(dt).cuda()
     W = (torch.randn(N, K, generator=g) / K ** 0.5).to(dt).cuda()
@@ -256,9 +253,8 @@ def test_gemm_256x256_tile(opname, dt, code, M, N, K, epi, pp):
     Ap, Wp = _padded(A, _rup(M, 256), Kp), _padded(W, _rup(N, 256), Kp)
     x0 = torch.randn(M, N, generator=g).cuda()
     outs = []
-    try:
-        for knob in (1, 0):
-            _lib.tune("gemm256_min_tiles", knob)
+    for knob in (1, 0):
+        with tuned(gemm_pp=pp, gemm256_min_tiles=knob):
             if epi == 2:
                 out = torch.cat([x0.clone(), torch.full((3, N), float("nan"), device="cuda")])
                 ldo = N
@@ -269,9 +265,6 @@ def test_gemm_256x256_tile(opname, dt, code, M, N, K, epi, pp):
                                            M, N, Kp, Kp, epi, _stream()), "gemm_terms")
             torch.cuda.synchronize()
             outs.append(out)
-    finally:
-        _lib.tune("gemm256_min_tiles", 192)
-        _lib.tune("gemm_pp", GEMM_PP_DEFAULT)
     y = A.float() @ W.float().t() + bias
     if epi == 1:
         y = F.gelu(y)
@@ -309,12 +302,9 @@ def test_gemm_ping_pong_repeatable_with_other_streams_on_the_chip():
         _lib.check(lib.fvit_gemm_bias_act(code, A.data_ptr(), K, W.data_ptr(), K, bias.data_ptr(), out.data_ptr(), N, M, N, K, 1, _stream()), "gemm")
         return out
 
-    try:
-        _lib.tune("gemm_pp", 0)
-        _lib.tune("gemm256_min_tiles", 0)
+    with tuned(gemm_pp=0, gemm256_min_tiles=0):
         ref = run()[:M].clone()
-        _lib.tune("gemm_pp", 1)
-        _lib.tune("gemm256_min_tiles", 192)
+    with tuned(gemm_pp=1):   # gemm256_min_tiles at its default: 36 x 12 tiles select the 256 x 256 form
         torch.cuda.synchronize()
         for it in range(24):
             for i, s2 in enumerate(side):
@@ -325,9 +315,6 @@ def test_gemm_ping_pong_repeatable_with_other_streams_on_the_chip():
             got = run()[:M]
             torch.cuda.synchronize()
             assert torch.equal(got, ref), f"iteration {it}: {(got.float() - ref.float()).abs().max().item()}"
-    finally:
-        _lib.tune("gemm_pp", GEMM_PP_DEFAULT)
-        _lib.tune("gemm256_min_tiles", 192)
 
 
 @pytest.mark.parametrize("opname,dt,code", OPS)
@@ -453,7 +440,6 @@ def test_ct_block_two_weight_terms(opname, dt, code, batch, G, use_add, use_gamm
     """fvit_ct_block_fused_terms: the carrier-token branch in one kernel with [hi image | lo image] weights in all four fragment arrays
     (variant 0: the 4-wave form, 3: the 8-wave form)."""
     lib = _lib.lib()
-    _lib.tune("ct_variant", variant)
     C, heads, hid = 256, 8, 1024
     g = torch.Generator(device="cpu").manual_seed(batch * 19 + G)
     rowsA = 4 * 53
@@ -487,10 +473,11 @@ def test_ct_block_two_weight_terms(opname, dt, code, batch, G, use_add, use_gamm
 
     def call(terms):
         out.fill_(float("nan"))
-        return lib.fvit_ct_block_fused_terms(code, X.data_ptr(), rowsA, src_idx.data_ptr(), p(add), out.data_ptr(), batch, G, heads, C, hid,
-                                             ln1w.data_ptr(), ln1b.data_ptr(), wqf.data_ptr(), bqh.data_ptr(), wpf.data_ptr(), bproj.data_ptr(),
-                                             p(g1), bp.data_ptr(), ctypes.c_float(32 ** -0.5), ln2w.data_ptr(), ln2b.data_ptr(), w1f.data_ptr(),
-                                             b1.data_ptr(), w2f.data_ptr(), b2.data_ptr(), p(g2), ctypes.c_float(1e-5), terms, _stream())
+        with tuned(ct_variant=variant):
+            return lib.fvit_ct_block_fused_terms(code, X.data_ptr(), rowsA, src_idx.data_ptr(), p(add), out.data_ptr(), batch, G, heads, C, hid,
+                                                 ln1w.data_ptr(), ln1b.data_ptr(), wqf.data_ptr(), bqh.data_ptr(), wpf.data_ptr(), bproj.data_ptr(),
+                                                 p(g1), bp.data_ptr(), ctypes.c_float(32 ** -0.5), ln2w.data_ptr(), ln2b.data_ptr(), w1f.data_ptr(),
+                                                 b1.data_ptr(), w2f.data_ptr(), b2.data_ptr(), p(g2), ctypes.c_float(1e-5), terms, _stream())
 
     def ref(two):
         ws = []
@@ -518,7 +505,6 @@ def test_ct_block_two_weight_terms(opname, dt, code, batch, G, use_add, use_gamm
     torch.cuda.synchronize()
     assert (out[:batch * G] - ref1).abs().max().item() < tol
     assert call(0) != 0
-    _lib.tune("ct_variant", CT_VARIANT_DEFAULT)
 
 
 @pytest.mark.parametrize("opname,dt,code", OPS)

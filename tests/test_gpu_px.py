@@ -14,7 +14,7 @@ import torch.nn.functional as F
 
 from fastervit_amd import _lib, hat_runtime
 from tests.cases import CASES
-from tests.util import build_product_model, case_input, load_golden, max_abs
+from tests.util import build_product_model, case_input, load_golden, max_abs, tuned
 
 pytestmark = pytest.mark.gpu
 
@@ -196,16 +196,11 @@ def test_conv3x3_px_patch_form(B, Ci, Co, H, W, act, in2, res, out):
     ol = _cl(torch.full((B, Co, H, W), nan, dtype=dt, device="cuda")) if out == "planes" else None
     of = _cl(torch.full((B, Co, H, W), nan, dtype=torch.float32, device="cuda")) if out == "f32" else None
     p = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
-    try:
-        _lib.tune("conv_patch", 1)
-        _lib.tune("conv_patch_max_waste_pct", 100000)
+    with tuned(conv_patch=1, conv_patch_max_waste_pct=100000):
         assert lib.fvit_conv3x3_patch_form(B, H, W, Ci, Co, 1) == 1
         _lib.check(lib.fvit_conv3x3_nhwc_px(1, xh.data_ptr(), p(xl) if in2 else None, wk.data_ptr(), bias.data_ptr(), p(rh), p(rl), p(oh), p(ol), p(of),
                                             B, H, W, Ci, Co, 1, act, 2, zeros.data_ptr(), _stream()), "conv3x3_px patch form")
         torch.cuda.synchronize()
-    finally:
-        _lib.tune("conv_patch", 1)
-        _lib.tune("conv_patch_max_waste_pct", 10)
     xin = xh.double() + (xl.double() if in2 else 0.0)
     ref = F.conv2d(xin.cpu(), (wh.double() + wl.double()), bias.double().cpu(), 1, 1)
     ref = [lambda t: t, torch.relu, lambda t: F.gelu(t)][act](ref)
@@ -315,9 +310,8 @@ def test_gemm_x3_dual_tiles_match_the_k_concatenated_walk():
         gamma = (torch.rand(N, generator=g) + 0.5).cuda()
         x0 = torch.randn(M, N, generator=g).cuda()
         outs = []
-        try:
-            for dual in (1, 0):
-                _lib.tune("gemm_x3_dual", dual)
+        for dual in (1, 0):
+            with tuned(gemm_x3_dual=dual):
                 if epi == 2:
                     out = x0.clone()
                     ldo, lo_off = N, 0
@@ -328,8 +322,6 @@ def test_gemm_x3_dual_tiles_match_the_k_concatenated_walk():
                                                   M, N, 3 * ka, ka, epi, _stream()), "gemm_terms_lo")
                 torch.cuda.synchronize()
                 outs.append(out.double().cpu() if epi == 2 else (out[:M, :N].double() + out[:M, Np:Np + N].double()).cpu())
-        finally:
-            _lib.tune("gemm_x3_dual", 1)
         ad, wd = ah.double() + al.double(), wh.double() + wl.double()
         ref = ad @ wd.t() + bias.double().cpu()
         if epi == 1:

@@ -10,6 +10,7 @@ import torch
 import torch.nn.functional as F
 
 from fastervit_amd import _lib, hat_runtime
+from tests.util import tuned
 
 OPS = {"f16": (torch.float16, 1), "bf16": (torch.bfloat16, 2)}
 SHAPES = [(256, 1), (256, 17), (256, 64), (256, 65), (256, 130), (512, 49), (512, 70), (512, 129)]   # 64-row workgroups: one partial, exact, one over, two + partial
@@ -50,16 +51,13 @@ class Case:
         M = x0.shape[0]
         xw = torch.cat([x0, torch.full((5, self.C), float("nan"), device="cuda")])
         gp = self.gamma.data_ptr() if use_gamma else None
-        _lib.tune("win_mlp_pipe", pipe)
-        try:
+        with tuned(win_mlp_pipe=pipe):
             if self.terms == 1:
                 rc = lib.fvit_win_mlp_fused(self.code, xw.data_ptr(), M, self.C, self.hid, self.lnw.data_ptr(), self.lnb.data_ptr(), ctypes.c_float(1e-5),
                                             self.w1p.data_ptr(), self.b1.data_ptr(), self.w2p.data_ptr(), self.b2.data_ptr(), gp, _stream())
             else:
                 rc = lib.fvit_win_mlp_fused_terms(self.code, xw.data_ptr(), M, self.C, self.hid, self.lnw.data_ptr(), self.lnb.data_ptr(), ctypes.c_float(1e-5),
                                                   self.w1p.data_ptr(), self.b1.data_ptr(), self.w2p.data_ptr(), self.b2.data_ptr(), gp, self.terms, _stream())
-        finally:
-            _lib.tune("win_mlp_pipe", 1)
         _lib.check(rc, "win_mlp_fused")
         torch.cuda.synchronize()
         assert torch.isnan(xw[M:]).all(), "rows behind M were written"
@@ -84,11 +82,8 @@ def replay_error(C, M, opname, terms, use_gamma, form256=2):
     case = Case(C, opname, terms, 1000 * C + M)
     x0 = (torch.randn(M, C, generator=case.g) * 1.5 + 0.3).cuda()
     ref = case.ref(x0, use_gamma)
-    _lib.tune("win_mlp256", form256)
-    try:
+    with tuned(win_mlp256=form256):
         plain, piped = case.launch(x0, use_gamma, pipe=0), case.launch(x0, use_gamma, pipe=1)
-    finally:
-        _lib.tune("win_mlp256", 2)
     assert torch.equal(plain, piped), "the plain and the pipelined loop differ"
     return (piped - ref).abs().max().item() / ref.abs().max().item()
 

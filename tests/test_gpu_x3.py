@@ -19,7 +19,7 @@ import torch.nn.functional as F
 
 from fastervit_amd import _lib
 from tests.cases import CASES
-from tests.util import build_product_model, case_input, load_golden, max_abs, rel_err
+from tests.util import build_product_model, case_input, load_golden, max_abs, rel_err, tuned
 
 pytestmark = pytest.mark.gpu
 
@@ -344,11 +344,8 @@ def test_gemm_residual_split_k(opname, dt, code, M, N, K):
     against the fp32 product, against the unsplit kernel (same products, other fp32 summation order), bitwise repeatable; a grid that fills the chip
     (the last shape) is not split and returns the unsplit kernel's bits."""
     lib = _lib.lib()
-    lib.fvit_tune(b"gemm_splitk", 1)   # opt-in knob (negative end to end under the stream shards, see fvit_gemm.hip)
-    try:
+    with tuned(gemm_splitk=1):   # opt-in knob (negative end to end under the stream shards, see fvit_gemm.hip)
         _split_k_body(lib, dt, code, M, N, K)
-    finally:
-        lib.fvit_tune(b"gemm_splitk", 0)
 
 
 def _split_k_body(lib, dt, code, M, N, K):
